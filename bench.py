@@ -12,6 +12,12 @@ there are no checkpoints offline. N>1 runs N independent engine replicas, one pe
 sequences are independent: data-parallel, weak scaling, no data-path collective); the reference's
 tensor-parallel mode is `tensor_parallel_size` of the engine itself.
 
+A plain run does only what the headline figure needs: engine start, W warm-up passes, K timed passes, one JSON line
+(metric, value, unit, higher_is_better, dtype, ms_per_step and the run's configuration). `--dump-outputs DIR` also
+writes what the last timed pass returned (see dump_outputs). Everything else described below — roofline replays, the
+CPU baseline and its parity verdict, the other BASELINE configs, the Qwen3-32B TP measurement of a multi-GPU run, the
+side files — runs only with `--full`.
+
 Rank 0 prints ONE JSON line (kept under 10 KB: the prose that explains its fields is `NOTES` below, also written to
 gpurun_out/bench_notes.json; the extras' full child lines go to gpurun_out/bench_extras_full.json). Besides the
 driver's fields it carries
@@ -71,6 +77,12 @@ def parse():
                     help="bench = BASELINE config 2/4 (reference bench.py); prefix = config 3 (512-token shared system "
                          "prompt x 256 seqs); long = config 5 (16 x 16,000-token prompts, 64 output tokens)")
     ap.add_argument("--num-seqs", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: roofline replays, the CPU baseline "
+                         "and parity, the other BASELINE configs (`extra_configs`), the TP extra of a multi-GPU run; the "
+                         "--no-* switches below take single legs out of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write what the last one returned as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-tp-extra", action="store_true",
@@ -84,7 +96,12 @@ def parse():
     ap.add_argument("--num-kvcache-blocks", type=int, default=-1)
     ap.add_argument("--kv-cache-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: opt-in OCP e4m3 KV cache (outside the reference's numerics; never the headline)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:       # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_roofline = args.no_tp_extra = args.no_extra_configs = True
+    return args
 
 
 def workload(num_seqs: int, kind: str = "bench"):
@@ -182,7 +199,7 @@ def main():
     if rank == 0:
         if "tp_qwen3_32b" in result and isinstance(result["tp_qwen3_32b"], dict):
             attach_tp_scaling(args, torch, result)
-        result["config"]["notes"] = write_notes(result)
+        result["config"]["notes"] = write_notes(result) if args.full else "bench.py::NOTES"
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()
@@ -304,12 +321,36 @@ def timed_passes(args, torch, dist, llm, world, backend, rec=None, sync_group=Tr
         if rec is not None:
             rec["on"] = (k == args.steps - 1) and not args.no_roofline
         llm.reset_prefix_cache()
-        llm.generate(prompts, sps, use_tqdm=False)
+        outs = llm.generate(prompts, sps, use_tqdm=False)
     sync_all()
     elapsed = time.perf_counter() - t0
     if rec is not None:
         rec["on"] = False
+    if args.dump_outputs and int(os.environ.get("RANK", "0")) == 0:
+        dump_outputs(args.dump_outputs, outs)
     return elapsed, prompts, out_lens
+
+
+def dump_outputs(path: str, outs: list) -> None:
+    """What the last timed pass returned to its caller, as arrays: generate() yields one completion per prompt, in
+    submission order. `token_ids.npy` = float32 [sequences, longest completion], row i = the token ids of completion i,
+    padded with -1 (ids < 2^24 are exact in float32); `lengths.npy` = float32 [sequences], the completions' lengths.
+    The headline workload makes 256 x 1024 values (1 MiB). The prompts, the sampling seed and the request ordinals the
+    draws are keyed by are functions of the arguments alone, so two builds run with the same arguments sample from the
+    same inputs and can be compared row by row."""
+    import numpy as np
+    toks = [o["token_ids"] for o in outs]
+    arr = np.full((len(toks), max((len(t) for t in toks), default=0)), -1.0, dtype=np.float32)
+    for i, t in enumerate(toks):
+        arr[i, :len(t)] = t
+    os.makedirs(path, exist_ok=True)
+    max_rows = (60 << 20) // (4 * max(arr.shape[1], 1))          # the dump stays under 64 MB
+    if len(toks) > max_rows:                                     # a fixed, seeded sample of the rows (`rows.npy` names them)
+        rows = np.sort(np.random.default_rng(0).choice(len(toks), max_rows, replace=False))
+        arr, toks = arr[rows], [toks[i] for i in rows]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "token_ids.npy"), arr)
+    np.save(os.path.join(path, "lengths.npy"), np.asarray([len(t) for t in toks], dtype=np.float32))
 
 
 def base_result(args, tp, world_engines, n_gpus, elapsed, total_out, llm, parallelism):
@@ -489,7 +530,7 @@ def extra_configs(args, torch) -> dict:
     gc.collect()
     torch.cuda.empty_cache()                       # the headline engine has exited: hand the GPU to the children
     out, full = {}, {}
-    common = ["--gpus", "1", "--steps", "1", "--no-cpu-baseline", "--no-extra-configs",
+    common = ["--gpus", "1", "--steps", "1", "--full", "--no-cpu-baseline", "--no-extra-configs",
               "--gpu-memory-utilization", str(args.gpu_memory_utilization)]
     # (one untimed warm-up pass where a pass is short — a 1.8 s pass measured cold carries the library GEMM's first-call
     #  set-up of every new prefill shape; the 20-35 s passes of the 32B runs stay cold)
@@ -555,9 +596,16 @@ def run_replica(args, torch, dist, rank, world, tp, backend):
     if rank == 0:       # which build of the library this run measures (NVL_LIBDIR selects another one for A/B runs)
         from nano_vllm_amd import ops as _ops
         print(f"[bench.py] library: {_ops.LIB_PATH}", file=sys.stderr, flush=True)
-
-    # ---- record decode batches of a pass (for the roofline replay) --------------------------
     runner = llm.model_runner
+    # (a run without the roofline leg — every plain run — leaves the engine as it is: nothing is wrapped or recorded)
+    rec, by_batch, host = (None, {}, {}) if args.no_roofline else instrument(llm, runner)
+    return measure_replica(args, torch, dist, rank, world, tp, backend, llm, runner, rec, by_batch, host)
+
+
+def instrument(llm, runner):
+    """Wrap the engine's step functions for the roofline leg: record the decode / prefill batches of the last timed pass
+    (`rec`), the decode time by batch size (`by_batch`) and the host-side time (`host`). Inactive until rec["on"]."""
+    # ---- record decode batches of a pass (for the roofline replay) --------------------------
     rec = {"on": False, "steps": 0, "ctx_tokens": 0, "samples": []}
     orig_prepare = runner.prepare_decode
 
@@ -631,7 +679,11 @@ def run_replica(args, torch, dist, rank, world, tp, backend):
     runner.prepare_decode = timed(runner.prepare_decode, "prepare_decode_s")
     # a prefill step starts on a drained queue and ends with a stream sync: its host wall time is its GPU time
     runner._run_prefill = timed(runner._run_prefill, "prefill_steps_s")
+    return rec, by_batch, host
 
+
+def measure_replica(args, torch, dist, rank, world, tp, backend, llm, runner, rec, by_batch, host):
+    """The warm-up and timed passes of run_replica's engine, then whatever legs of --full apply."""
     try:
         elapsed, prompts, out_lens = timed_passes(args, torch, dist, llm, world, backend, rec)
     except Exception as ex:  # noqa: BLE001 — a latched P2P collective surfaced inside generate(): re-run over the process group

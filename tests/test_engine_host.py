@@ -573,6 +573,28 @@ def test_bench_line_stays_compact(monkeypatch, tmp_path):
     assert len(_json.dumps(bench.NOTES)) < 6000 and bench.write_notes({}).startswith("gpurun_out/")
 
 
+def test_bench_plain_run_is_lean_and_dumps_what_generate_returned(monkeypatch, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` has every side leg switched off (they run with --full, where the
+    --no-* switches still take single legs out), and --dump-outputs writes the completions of the last timed pass."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    legs = ("no_cpu_baseline", "no_roofline", "no_tp_extra", "no_extra_configs")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None) and all(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-roofline", "--dump-outputs", str(tmp_path / "d")])
+    a = bench.parse()
+    assert a.full and a.no_roofline and not (a.no_cpu_baseline or a.no_tp_extra or a.no_extra_configs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    outs = [{"text": "", "token_ids": [5, 6, 7]}, {"text": "", "token_ids": [151935]}, {"text": "", "token_ids": []}]
+    bench.dump_outputs(a.dump_outputs, outs)
+    toks, lens = np.load(tmp_path / "d" / "token_ids.npy"), np.load(tmp_path / "d" / "lengths.npy")
+    assert toks.dtype == np.float32 and lens.dtype == np.float32 and sorted(os.listdir(tmp_path / "d")) == ["lengths.npy", "token_ids.npy"]
+    assert toks.tolist() == [[5, 6, 7], [151935, -1, -1], [-1, -1, -1]] and lens.tolist() == [3, 1, 0]
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # ops.P2PComm construction is collective: a rank that fails locally must still join the exchange and the barrier
 class _FakeCommLib:

@@ -15,7 +15,7 @@ tests)
 tptests)
   timeout 900 python -m pytest tests/test_tp_gpu.py -m gpu -q -rf -s > $OUT/pytest_tp.log 2>&1; echo "tp pytest rc=$?" | tee -a $OUT/pytest_tp.log; tail -40 $OUT/pytest_tp.log;;
 bench)
-  timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 3000 $OUT/bench.json;;
+  timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 3000 $OUT/bench.json;;
 prof)
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --truncate-kernels -f csv -d /tmp/prof_replay -o replay -- python $REPO/tools/attn_replay.py --fused > $OUT/replay_under_rocprof.json 2> $OUT/replay_prof.err; echo "prof rc=$?")
   f=$(find /tmp/prof_replay -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $OUT/replay_kernel_stats.csv && head -5 $OUT/replay_kernel_stats.csv;;
@@ -23,7 +23,7 @@ pmc)
   (cd /tmp && timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex 'decode_' -f csv -d /tmp/pmc_replay -o replay -- python $REPO/tools/attn_replay.py --fused --reps 1 > $OUT/replay_under_pmc.json 2> $OUT/replay_pmc.err; echo "pmc rc=$?")
   python tools/pmc_summary.py /tmp/pmc_replay $OUT/pmc_fetch_summary.json | tail -30;;
 benchprof)
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --truncate-kernels -f csv -d /tmp/prof_bench -o bench -- python $REPO/bench.py --no-cpu-baseline --no-extra-configs > $OUT/bench_under_rocprof.json 2> $OUT/bench_prof.err; echo "benchprof rc=$?")
+  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --truncate-kernels -f csv -d /tmp/prof_bench -o bench -- python $REPO/bench.py --full --no-cpu-baseline --no-extra-configs > $OUT/bench_under_rocprof.json 2> $OUT/bench_prof.err; echo "benchprof rc=$?")
   f=$(find /tmp/prof_bench -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $OUT/bench_kernel_stats.csv && head -12 $OUT/bench_kernel_stats.csv | cut -c1-200;;
 probe)
   timeout 600 python tools/gpu_probe.py > $OUT/probe.log 2>&1; cp gpurun_out/probe.json $OUT/ 2>/dev/null; tail -3 $OUT/probe.log;;
@@ -37,7 +37,7 @@ newtests)
   timeout 1200 python -m pytest tests -m gpu -q -rf -k "lmhead or prefill or logits or tiny_model_greedy or tp2 or sampler or 06b_shape_greedy" > $OUT/pytest_new.log 2>&1; echo "newtests rc=$?"; grep -E "^(FAILED|ERROR)|passed|failed" $OUT/pytest_new.log | tail -20;;
 fp8)
   timeout 900 python -m pytest tests -m gpu -q -rf -k "fp8" > $OUT/pytest_fp8.log 2>&1; echo "fp8 tests rc=$?"; grep -E "^(FAILED|ERROR)|passed|failed|fp8 KV vs" $OUT/pytest_fp8.log | tail -12
-  timeout 600 python bench.py --kv-cache-dtype fp8 --no-cpu-baseline > $OUT/bench_fp8kv.json 2> $OUT/bench_fp8kv.err; echo "bench fp8 rc=$?"; tail -c 400 $OUT/bench_fp8kv.err; cut -c1-1500 $OUT/bench_fp8kv.json;;
+  timeout 600 python bench.py --full --kv-cache-dtype fp8 --no-cpu-baseline > $OUT/bench_fp8kv.json 2> $OUT/bench_fp8kv.err; echo "bench fp8 rc=$?"; tail -c 400 $OUT/bench_fp8kv.err; cut -c1-1500 $OUT/bench_fp8kv.json;;
 px)
   # shared-prefix attention pass: kernel parity, engine parity, config 3 A/B (pass off / on, alternating), headline sanity.
   # "old" = another commit's tree built in a worktree next to this one (git worktree add -f _ab_old <commit>; build() there):
@@ -47,7 +47,7 @@ px)
   for x in old 0 1 old 0 1; do
     [ $x = old ] && [ ! -d _ab_old ] && continue
     if [ $x = old ]; then (cd _ab_old && timeout 300 python bench.py --model qwen3-8b --workload prefix --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cfg3_px$x.json 2> $OUT/cfg3_px$x.err)
-    else NVL_SHARED_PREFIX=$x timeout 300 python bench.py --model qwen3-8b --workload prefix --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cfg3_px$x.json 2> $OUT/cfg3_px$x.err; fi
+    else NVL_SHARED_PREFIX=$x timeout 300 python bench.py --full --model qwen3-8b --workload prefix --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cfg3_px$x.json 2> $OUT/cfg3_px$x.err; fi
     echo "cfg3 px=$x rc=$?"; tail -c 300 $OUT/cfg3_px$x.err | grep -v amdgpu.ids; python -c "
 import json,sys
 d=json.loads([l for l in open('$OUT/cfg3_px$x.json') if l.startswith('{')][-1])
@@ -56,7 +56,7 @@ r=d['roofline']; print('px=$x', round(d['value']), 'tok/s', round(d['ms_per_step
   for x in old new old new; do
     [ $x = old ] && [ ! -d _ab_old ] && continue
     if [ $x = old ]; then (cd _ab_old && timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --steps 2 --warmup 1 > $OUT/headline_$x.json 2> $OUT/headline_$x.err)
-    else timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --steps 2 --warmup 1 > $OUT/headline_$x.json 2> $OUT/headline_$x.err; fi
+    else timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs --steps 2 --warmup 1 > $OUT/headline_$x.json 2> $OUT/headline_$x.err; fi
     echo "headline $x rc=$?"; python -c "
 import json
 d=json.loads([l for l in open('$OUT/headline_$x.json') if l.startswith('{')][-1])
@@ -66,14 +66,14 @@ px2)
   # after the prefix kernel's load reorder: kernel parity again, config 3 with the pass (child-style env), and the headline
   # with / without a small OpenMP pool (the host loop's torch ops)
   timeout 400 python -m pytest tests/test_shared_prefix_gpu.py -q -rf > $OUT/pytest_px_kernel.log 2>&1; echo "px kernel rc=$?"; grep -E "^(FAILED|ERROR)|passed|failed|Error" $OUT/pytest_px_kernel.log | tail -30
-  for x in 1 0 1; do NVL_SHARED_PREFIX=$x OMP_NUM_THREADS=8 timeout 300 python bench.py --model qwen3-8b --workload prefix --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cfg3_px$x.json 2> $OUT/cfg3_px$x.err; python -c "
+  for x in 1 0 1; do NVL_SHARED_PREFIX=$x OMP_NUM_THREADS=8 timeout 300 python bench.py --full --model qwen3-8b --workload prefix --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cfg3_px$x.json 2> $OUT/cfg3_px$x.err; python -c "
 import json
 d=json.loads([l for l in open('$OUT/cfg3_px$x.json') if l.startswith('{')][-1])
 r=d['roofline']; print('px=$x omp8', round(d['value']), 'tok/s; attn', round(r['avg_launch_us'],1), 'us frac', round(r['frac'],3), 'step', d['config']['decode_ms_per_step_by_batch']['ms_per_step'])
 "; cp $OUT/cfg3_px$x.json $OUT/cfg3_px${x}_run_$(date +%s).json; done
   for x in unset 8 unset 8; do
-    if [ $x = unset ]; then timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --steps 2 --warmup 1 > $OUT/headline_omp$x.json 2> $OUT/headline_omp$x.err
-    else OMP_NUM_THREADS=$x timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --steps 2 --warmup 1 > $OUT/headline_omp$x.json 2> $OUT/headline_omp$x.err; fi
+    if [ $x = unset ]; then timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs --steps 2 --warmup 1 > $OUT/headline_omp$x.json 2> $OUT/headline_omp$x.err
+    else OMP_NUM_THREADS=$x timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs --steps 2 --warmup 1 > $OUT/headline_omp$x.json 2> $OUT/headline_omp$x.err; fi
     python -c "
 import json
 d=json.loads([l for l in open('$OUT/headline_omp$x.json') if l.startswith('{')][-1])
@@ -81,7 +81,7 @@ print('omp=$x', round(d['value']), 'tok/s attn', round(d['roofline']['avg_launch
 "; cp $OUT/headline_omp$x.json $OUT/headline_omp${x}_run_$(date +%s).json; done;;
 pxprof)
   # rocprofv3 kernel stats of config 3 without / with the shared-prefix pass (same box)
-  for x in 0 1; do (cd /tmp && NVL_SHARED_PREFIX=$x OMP_NUM_THREADS=8 timeout 400 rocprofv3 --kernel-trace --stats --truncate-kernels -f csv -d /tmp/prof_cfg3_px$x -o cfg3 -- python $REPO/bench.py --model qwen3-8b --workload prefix --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cfg3_px${x}_under_rocprof.json 2> $OUT/cfg3_px${x}_prof.err; echo "pxprof $x rc=$?")
+  for x in 0 1; do (cd /tmp && NVL_SHARED_PREFIX=$x OMP_NUM_THREADS=8 timeout 400 rocprofv3 --kernel-trace --stats --truncate-kernels -f csv -d /tmp/prof_cfg3_px$x -o cfg3 -- python $REPO/bench.py --full --model qwen3-8b --workload prefix --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cfg3_px${x}_under_rocprof.json 2> $OUT/cfg3_px${x}_prof.err; echo "pxprof $x rc=$?")
     f=$(find /tmp/prof_cfg3_px$x -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $OUT/cfg3_px${x}_kernel_stats.csv && head -14 $OUT/cfg3_px${x}_kernel_stats.csv | cut -c1-160
     python -c "
 import json
@@ -89,7 +89,7 @@ d=json.loads([l for l in open('$OUT/cfg3_px${x}_under_rocprof.json') if l.starts
 print('px=$x (under rocprof, OMP 8)', round(d['value']), 'tok/s step', d['config']['decode_ms_per_step_by_batch']['ms_per_step'])
 "; done;;
 cfg3)
-  timeout 900 python bench.py --model qwen3-8b --workload prefix --no-cpu-baseline --warmup 0 > $OUT/bench_cfg3_8b_prefix.json 2> $OUT/bench_cfg3.err; echo "cfg3 rc=$?"; tail -c 300 $OUT/bench_cfg3.err; cut -c1-1200 $OUT/bench_cfg3_8b_prefix.json;;
+  timeout 900 python bench.py --full --model qwen3-8b --workload prefix --no-cpu-baseline --warmup 0 > $OUT/bench_cfg3_8b_prefix.json 2> $OUT/bench_cfg3.err; echo "cfg3 rc=$?"; tail -c 300 $OUT/bench_cfg3.err; cut -c1-1200 $OUT/bench_cfg3_8b_prefix.json;;
 tpfunc)
   timeout 600 python tools/tp_functional.py qwen3-32b 2 8 48 > $OUT/tp_functional_32b_tp2.json 2> $OUT/tp_functional.err; echo "tpfunc rc=$?"; tail -c 800 $OUT/tp_functional.err; cat $OUT/tp_functional_32b_tp2.json;;
 pmcprefill)
@@ -103,14 +103,14 @@ tprun)
   # (functional: NVL_BENCH_SHARE_GPU=1 + gloo). (a) default model: 2 data-parallel replicas + the Qwen3-32B TP=2 extra;
   # (b) --tp 2 as the primary metric on Qwen3-0.6B shapes.
   export NVL_BENCH_SHARE_GPU=1 NVL_BENCH_BACKEND=gloo
-  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 1 --warmup 0 --num-seqs 48 --gpu-memory-utilization 0.3 --num-kvcache-blocks 300 --no-cpu-baseline --no-roofline > $OUT/torchrun_dp2_plus_tp_extra.json 2> $OUT/torchrun_dp2.err; echo "torchrun dp2+extra rc=$?"; grep -v "socket.cpp\|Gloo\|amdgpu.ids" $OUT/torchrun_dp2.err | tail -15; cat $OUT/torchrun_dp2_plus_tp_extra.json
-  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --tp 2 --steps 1 --warmup 0 --num-seqs 48 --num-kvcache-blocks 300 --no-cpu-baseline > $OUT/torchrun_tp2_qwen3-0.6b.json 2> $OUT/torchrun_tp2.err; echo "torchrun tp2 rc=$?"; grep -v "socket.cpp\|Gloo\|amdgpu.ids" $OUT/torchrun_tp2.err | tail -15; cat $OUT/torchrun_tp2_qwen3-0.6b.json
+  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 1 --warmup 0 --num-seqs 48 --gpu-memory-utilization 0.3 --num-kvcache-blocks 300 --no-cpu-baseline --no-roofline > $OUT/torchrun_dp2_plus_tp_extra.json 2> $OUT/torchrun_dp2.err; echo "torchrun dp2+extra rc=$?"; grep -v "socket.cpp\|Gloo\|amdgpu.ids" $OUT/torchrun_dp2.err | tail -15; cat $OUT/torchrun_dp2_plus_tp_extra.json
+  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 2 --tp 2 --steps 1 --warmup 0 --num-seqs 48 --num-kvcache-blocks 300 --no-cpu-baseline > $OUT/torchrun_tp2_qwen3-0.6b.json 2> $OUT/torchrun_tp2.err; echo "torchrun tp2 rc=$?"; grep -v "socket.cpp\|Gloo\|amdgpu.ids" $OUT/torchrun_tp2.err | tail -15; cat $OUT/torchrun_tp2_qwen3-0.6b.json
   unset NVL_BENCH_SHARE_GPU NVL_BENCH_BACKEND;;
 tprun2)
   export NVL_BENCH_SHARE_GPU=1 NVL_BENCH_BACKEND=gloo
   for v in "lean" "fenced"; do
     export NVL_TP_P2P_HANDOFF=$v
-    T0=$(date +%s); timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 2 --tp 2 --steps 1 --warmup 0 --num-seqs 48 --num-kvcache-blocks 300 --no-cpu-baseline > $OUT/torchrun_tp2_$v.json 2> $OUT/torchrun_tp2_$v.err; echo "torchrun tp2 $v rc=$? wall=$(( $(date +%s) - T0 )) s"; grep -v "socket.cpp\|Gloo\|amdgpu.ids\|OMP_NUM\|\*\*\*" $OUT/torchrun_tp2_$v.err | tail -6; cut -c1-700 $OUT/torchrun_tp2_$v.json; echo
+    T0=$(date +%s); timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29535 bench.py --full --gpus 2 --tp 2 --steps 1 --warmup 0 --num-seqs 48 --num-kvcache-blocks 300 --no-cpu-baseline > $OUT/torchrun_tp2_$v.json 2> $OUT/torchrun_tp2_$v.err; echo "torchrun tp2 $v rc=$? wall=$(( $(date +%s) - T0 )) s"; grep -v "socket.cpp\|Gloo\|amdgpu.ids\|OMP_NUM\|\*\*\*" $OUT/torchrun_tp2_$v.err | tail -6; cut -c1-700 $OUT/torchrun_tp2_$v.json; echo
   done
   unset NVL_BENCH_SHARE_GPU NVL_BENCH_BACKEND NVL_TP_P2P_HANDOFF;;
 prefillw)
@@ -156,7 +156,7 @@ mfmafp8)
 tprun1)
   # only the data-parallel line + the Qwen3-32B TP extra (a separate child job per rank), both ranks on the ONE GPU
   export NVL_BENCH_SHARE_GPU=1 NVL_BENCH_BACKEND=gloo NVL_BENCH_TP_EXTRA_TIMEOUT=400
-  timeout 700 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 1 --warmup 0 --num-seqs 48 --gpu-memory-utilization 0.3 --num-kvcache-blocks 300 --no-cpu-baseline --no-roofline > $OUT/torchrun_dp2_plus_tp_extra.json 2> $OUT/torchrun_dp2.err; echo "torchrun dp2+extra rc=$?"; grep -v "socket.cpp\|Gloo\|amdgpu.ids\|OMP_NUM\|\*\*\*" $OUT/torchrun_dp2.err | tail -8; cut -c1-2500 $OUT/torchrun_dp2_plus_tp_extra.json
+  timeout 700 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 1 --warmup 0 --num-seqs 48 --gpu-memory-utilization 0.3 --num-kvcache-blocks 300 --no-cpu-baseline --no-roofline > $OUT/torchrun_dp2_plus_tp_extra.json 2> $OUT/torchrun_dp2.err; echo "torchrun dp2+extra rc=$?"; grep -v "socket.cpp\|Gloo\|amdgpu.ids\|OMP_NUM\|\*\*\*" $OUT/torchrun_dp2.err | tail -8; cut -c1-2500 $OUT/torchrun_dp2_plus_tp_extra.json
   unset NVL_BENCH_SHARE_GPU NVL_BENCH_BACKEND NVL_BENCH_TP_EXTRA_TIMEOUT;;
 pmcg)
   # HBM traffic (FETCH_SIZE) of the decode-attention kernel at every group size the BASELINE configs run:
@@ -185,7 +185,7 @@ pmcpx)
 tp3)
   timeout 1500 python -m pytest tests -m gpu -q -rf -s -k "tp or cpu_oracle or fp8_kv_store or rccl or p2p" --durations=8 > $OUT/pytest_tp3.log 2>&1; echo "tp3 pytest rc=$?"; grep -E "^(FAILED|ERROR)|passed|failed|argmax|device-resident" $OUT/pytest_tp3.log | tail -30;;
 benchfull)
-  T0=$(date +%s); timeout 1500 python bench.py ${BENCH_ARGS:-} > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench rc=$? wall=$(( $(date +%s) - T0 )) s"; tail -c 400 $OUT/bench_full.err; python -c "
+  T0=$(date +%s); timeout 1500 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench rc=$? wall=$(( $(date +%s) - T0 )) s"; tail -c 400 $OUT/bench_full.err; python -c "
 import json; d=json.load(open('$OUT/bench_full.json')); print(round(d['value']), d['roofline']['frac'], d['roofline']['decode_step']['frac_of_8TBps'], d.get('cpu_baseline')); [print(k, v.get('value'), v.get('error'), v.get('wall_s_incl_engine_start'), (v.get('roofline') or {}).get('frac'), (v.get('roofline') or {}).get('traffic'), (v.get('roofline_prefill') or {}).get('achieved')) for k, v in d.get('extra_configs', {}).items()]";;
 pmcprefillfetch)
   (cd /tmp && rm -rf /tmp/pmc_pf_fetch && timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex prefill_attn -f csv -d /tmp/pmc_pf_fetch -o pf -- python $REPO/tools/prefill_bench.py > $OUT/prefill_under_pmc_fetch.json 2> $OUT/prefill_pmc_fetch.err; echo "pmcprefillfetch rc=$?")
@@ -257,7 +257,7 @@ first8)
   timeout 600 python tools/p2p_bench.py $N $P2PMODE > $OUT/first8_p2p_vs_rccl_w$N.json 2> $OUT/first8_p2p.err; echo "first8 p2p rc=$?"; tail -c 300 $OUT/first8_p2p.err | grep -v amdgpu.ids; cut -c1-1500 $OUT/first8_p2p_vs_rccl_w$N.json
   for t in 2 4 8; do
     [ $t -gt $N ] && continue
-    T0=$(date +%s); timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $t --master-addr 127.0.0.1 --master-port $((29600 + t)) bench.py --gpus $t --tp $t --model $MODEL --steps 1 --warmup 0 --no-cpu-baseline --no-extra-configs $SEQS > $OUT/first8_tp$t.json 2> $OUT/first8_tp$t.err; echo "first8 tp=$t rc=$? wall=$(( $(date +%s) - T0 )) s"
+    T0=$(date +%s); timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $t --master-addr 127.0.0.1 --master-port $((29600 + t)) bench.py --full --gpus $t --tp $t --model $MODEL --steps 1 --warmup 0 --no-cpu-baseline --no-extra-configs $SEQS > $OUT/first8_tp$t.json 2> $OUT/first8_tp$t.err; echo "first8 tp=$t rc=$? wall=$(( $(date +%s) - T0 )) s"
     grep -v "socket.cpp\|Gloo\|amdgpu.ids\|OMP_NUM\|\*\*\*" $OUT/first8_tp$t.err | tail -4; python - $OUT/first8_tp$t.json <<'PY'
 import json, sys
 try:

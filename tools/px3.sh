@@ -12,7 +12,7 @@ n=0
 for x in ${ARMS:-3 4 3 4}; do
   n=$((n+1))
   export NVL_PX_ITEMS_PER_WG=$x
-  OMP_NUM_THREADS=8 timeout 300 python bench.py --model qwen3-8b --workload prefix --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cfg3_${x}_$n.json 2> $OUT/cfg3_${x}_$n.err
+  OMP_NUM_THREADS=8 timeout 300 python bench.py --full --model qwen3-8b --workload prefix --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cfg3_${x}_$n.json 2> $OUT/cfg3_${x}_$n.err
   python -c "
 import json
 d=json.loads([l for l in open('$OUT/cfg3_${x}_$n.json') if l.startswith('{')][-1])

@@ -5,7 +5,7 @@ OUT=gpurun_out/${TAG:-r06ae}; mkdir -p $OUT
 for m in ${MODELS:-qwen3-0.6b qwen3-8b}; do for n in ${SEQS:-48 96 160 256}; do for mode in off on; do
   unset NVL_SHARED_PREFIX NVL_SHARED_PREFIX_MIN_MB
   if [ $mode = off ]; then export NVL_SHARED_PREFIX=0; else export NVL_SHARED_PREFIX_MIN_MB=0; fi
-  OMP_NUM_THREADS=8 timeout 200 python bench.py --model $m --workload prefix --num-seqs $n --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cx_${m}_${n}_$mode.json 2> $OUT/cx_${m}_${n}_$mode.err
+  OMP_NUM_THREADS=8 timeout 200 python bench.py --full --model $m --workload prefix --num-seqs $n --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cx_${m}_${n}_$mode.json 2> $OUT/cx_${m}_${n}_$mode.err
   python -c "
 import json
 d=json.loads([l for l in open('$OUT/cx_${m}_${n}_$mode.json') if l.startswith('{')][-1])
@@ -16,7 +16,7 @@ done; done; done
 if [ "${FP8:-1}" = 1 ]; then for m in qwen3-0.6b qwen3-8b; do for mode in off on; do
   unset NVL_SHARED_PREFIX NVL_SHARED_PREFIX_MIN_MB
   if [ $mode = off ]; then export NVL_SHARED_PREFIX=0; else export NVL_SHARED_PREFIX=1 NVL_SHARED_PREFIX_MIN_MB=0; fi
-  OMP_NUM_THREADS=8 timeout 200 python bench.py --model $m --workload prefix --kv-cache-dtype fp8 --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cx_fp8_${m}_$mode.json 2> $OUT/cx_fp8_${m}_$mode.err
+  OMP_NUM_THREADS=8 timeout 200 python bench.py --full --model $m --workload prefix --kv-cache-dtype fp8 --warmup 1 --steps 1 --no-cpu-baseline --no-extra-configs > $OUT/cx_fp8_${m}_$mode.json 2> $OUT/cx_fp8_${m}_$mode.err
   python -c "
 import json
 d=json.loads([l for l in open('$OUT/cx_fp8_${m}_$mode.json') if l.startswith('{')][-1])
