@@ -134,6 +134,26 @@ int nvl_linear_wide(const void* x, const void* weight, void* out, int64_t m, int
                     int weight_layout, void* workspace, size_t workspace_bytes, void* stream);
 int nvl_pack_weight_tiles(const void* weight, void* packed, int64_t n, int64_t k, void* stream);
 
+/* Weight-only FP8 (W8A16) variant of nvl_linear_wide (opt-in: LLM(..., weight_dtype="fp8")):
+ *   out[m, n] = x[m, k] (bf16) . (W8[n, k] (OCP e4m3) o S)^T
+ * S is fp32, one value per (16-row weight tile, 128-column k block): scales[n/16][k/128].
+ * Per k block the products of x and the fp8 values (converted to bf16 exactly) are summed in
+ * fp32; the block sum is multiplied by its scale in fp32 and added to the fp32 accumulator.
+ * Scaled weights are never rounded to bf16; scales are arbitrary fp32. Modes, output shapes,
+ * slab conventions and rounding points are nvl_linear_wide's. m = 1 ... 256, n % 16 == 0
+ * (mode 1: n % 32 == 0), k % 128 == 0.
+ *   nvl_linear_wide_fp8_plan: as nvl_linear_wide_plan (pure host code): 1 / 0, *splits,
+ *     *workspace_bytes (modes 0 / 1 with a K split).
+ *   nvl_linear_wide_fp8: NVL_EUNSUPPORTED ("not covered") when the plan query says 0.
+ *   nvl_pack_weight_tiles_fp8: packed[n/16][k/64][64 lanes][16 bytes] <- w8[n][k] (one byte per
+ *     value, n % 16 == 0, k % 64 == 0): lane = 16 * (k % 32 / 8) + row % 16 holds its A-operand
+ *     fragments of two consecutive 32-wide k blocks of v_mfma_f32_16x16x32_bf16 (bytes 0-7:
+ *     k = 64 j + 8 (lane / 16) ..., bytes 8-15: 32 columns further). Done once at load time. */
+int nvl_linear_wide_fp8_plan(int64_t m, int n, int k, int mode, int* splits, size_t* workspace_bytes);
+int nvl_linear_wide_fp8(const void* x, const void* w8_packed, const void* scales, void* out, int64_t m,
+                        int n, int k, int mode, void* workspace, size_t workspace_bytes, void* stream);
+int nvl_pack_weight_tiles_fp8(const void* w8, void* packed, int64_t n, int64_t k, void* stream);
+
 /* Fused split-K reduction + residual add + RMSNorm: replaces
  * RMSNorm.add_rms_forward (layers/layernorm.py:28-40) when its input is the
  * fp32 partials of nvl_linear_decode mode 2:

@@ -10,6 +10,10 @@ Extensions (all optional, behaviour-neutral when unset):
     *.safetensors (no 8B/32B checkpoints exist offline).
   * Config.kv_cache_dtype = "fp8" stores K/V as OCP fp8 e4m3: the decode step is bound by
     K/V bytes, this halves them. It changes numerics, so every parity run keeps the default "bf16".
+  * Config.weight_dtype = "fp8" quantises the decode projections (q|k|v, o, gate|up, down) at load time to OCP e4m3
+    with a power-of-two scale per 128 x 128 block and streams them through nvl_linear_wide_fp8 (half the weight bytes
+    per decode step, a half-size packed copy). The bf16 parameter is overwritten with the dequantised values, so
+    prefill and decode compute with the same matrix. Outside the reference's numerics: opt-in, default "bf16".
 """
 from __future__ import annotations
 
@@ -45,6 +49,7 @@ class Config:
     seed: int = 0
     dummy_weights: bool = False
     kv_cache_dtype: str = "bf16"         # "fp8": OCP e4m3 KV cache (halves decode bytes; outside the reference's numerics)
+    weight_dtype: str = "bf16"           # "fp8": block-scaled e4m3 decode projections (halves weight bytes; same caveat)
 
     def __post_init__(self):
         assert os.path.isdir(self.model), f"model directory not found: {self.model}"
@@ -56,6 +61,7 @@ class Config:
         self.max_model_len = min(self.max_model_len, self.hf_config.max_position_embeddings)
         assert self.max_num_batched_tokens >= 1 and self.max_num_seqs >= 1
         assert self.kv_cache_dtype in ("bf16", "fp8"), "kv_cache_dtype must be 'bf16' or 'fp8'"
+        assert self.weight_dtype in ("bf16", "fp8"), "weight_dtype must be 'bf16' or 'fp8'"
 
 
 def model_geometry(hf_config, tp: int = 1) -> dict:

@@ -356,7 +356,10 @@ class ModelRunner:
         used = skipped = 0
         for m in self.model.modules():
             if isinstance(m, (LinearBase, ParallelLMHead)):
-                got = m.pack_for_decode(budget - used)
+                if isinstance(m, LinearBase):      # (lm_head and embedding stay bf16, as in the published FP8 checkpoints)
+                    got = m.pack_for_decode(budget - used, weight_dtype=self.config.weight_dtype)
+                else:
+                    got = m.pack_for_decode(budget - used)
                 if got < 0:
                     skipped += 1
                 else:

@@ -255,8 +255,40 @@ class LinearBase(nn.Module):
         else:
             self.register_parameter("bias", None)
         self.weight_packed: torch.Tensor | None = None     # tile-packed copy for nvl_linear_wide (pack_for_decode)
+        self.weight_fp8_packed: torch.Tensor | None = None # e4m3 tile-packed copy + its [N/16, K/128] fp32 scales for
+        self.weight_scale: torch.Tensor | None = None      # nvl_linear_wide_fp8 (pack_for_decode(weight_dtype="fp8"))
 
-    def pack_for_decode(self, budget_bytes: float = float("inf")) -> int:
+    def _pack_fp8(self, budget_bytes: float) -> int | None:
+        """weight_dtype="fp8": quantise this rank's weight as loaded (the merged q|k|v / gate|up matrix) in 128 x 128
+        blocks anchored at (0, 0) to OCP e4m3 with the power-of-two scale 2^ceil(log2(amax / 448)) (1 for an all-zero
+        block), OVERWRITE the bf16 parameter with the dequantised values (exact in bf16 for power-of-two scales, so the
+        prefill-sized library GEMM and the fp8 decode kernel compute with one and the same matrix) and keep the e4m3
+        tile-packed copy + per-(16-row tile, k block) scales instead of the bf16 packed copy. None: shape not covered by
+        nvl_linear_wide_fp8 (the projection keeps today's path)."""
+        n, k = self.weight.shape
+        if k % 128 or ops.linear_wide_fp8_plan(144, n, k, ops.LINEAR_BF16) is None:
+            return None
+        if n * k + (n // 16) * (k // 128) * 4 > budget_bytes:
+            return -1
+        w = self.weight.data
+        nb = (n + 127) // 128
+        amax = torch.zeros((nb, k // 128), dtype=torch.float32, device=w.device)
+        for b in range(nb):                                   # (per 128-row band: no fp32 copy of the whole matrix)
+            band = w[b * 128:(b + 1) * 128].float()
+            amax[b] = band.view(band.shape[0], k // 128, 128).abs().amax(dim=(0, 2))
+        scale = torch.where(amax > 0, torch.exp2(torch.ceil(torch.log2(amax / 448.0))), torch.ones_like(amax))
+        rows = scale.repeat_interleave(128, 0)[:n]            # [n, k/128]
+        w8 = torch.empty((n, k), dtype=torch.float8_e4m3fn, device=w.device)
+        for b in range(nb):
+            sl = slice(b * 128, min((b + 1) * 128, n))
+            q = (w[sl].float().view(-1, k // 128, 128) / rows[sl].unsqueeze(-1)).view(-1, k).to(torch.float8_e4m3fn)
+            w8[sl] = q
+            w[sl] = (q.float().view(-1, k // 128, 128) * rows[sl].unsqueeze(-1)).view(-1, k).to(w.dtype)
+        self.weight_fp8_packed = ops.pack_weight_tiles_fp8(w8)
+        self.weight_scale = scale.repeat_interleave(8, 0)[:n // 16].contiguous()
+        return n * k + self.weight_scale.numel() * 4
+
+    def pack_for_decode(self, budget_bytes: float = float("inf"), weight_dtype: str = "bf16") -> int:
         """After the weights are loaded: keep a tile-packed copy (ops.pack_weight_tiles) of a projection whose decode
         GEMM is one of the hand-written kernels — the skinny kernel (K <= 1024-3072: Qwen3-0.6B) or the wide-tile one
         (deep reductions: Qwen3-8B / 32B shapes). The row-major parameter stays: prefill-sized GEMMs run on hipBLASLt
@@ -266,6 +298,10 @@ class LinearBase(nn.Module):
         if (self.bias is not None or not self.weight.is_cuda or n % 16 or k % 32
                 or os.environ.get("NVL_PACKED_WEIGHTS", "1") == "0"):
             return 0
+        if weight_dtype == "fp8":
+            got = self._pack_fp8(budget_bytes)
+            if got is not None:
+                return got
         skinny = any(ops.linear_decode_splits(144, n, k, mode) for mode in (ops.LINEAR_BF16, ops.LINEAR_PARTIAL))
         wide = (k % 128 == 0 and os.environ.get("NVL_GEMM_WIDE", "auto") != "0"
                 and ops.linear_wide_plan(144, n, k, ops.LINEAR_BF16) is not None)
@@ -276,6 +312,10 @@ class LinearBase(nn.Module):
         self.weight_packed = ops.pack_weight_tiles(self.weight.data)
         return self.weight_packed.numel() * 2
 
+    def _fp8(self):
+        """(e4m3 tile-packed weight, scales) of a projection packed with weight_dtype="fp8", else None."""
+        return None if self.weight_fp8_packed is None else (self.weight_fp8_packed, self.weight_scale)
+
     def _my_slice(self, loaded: torch.Tensor, dim: int) -> torch.Tensor:
         size = loaded.shape[dim] // self.tp_size
         return loaded.narrow(dim, self.tp_rank * size, size)
@@ -285,7 +325,7 @@ class LinearBase(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.bias is None and _decode_sized(x):
-            y = decode_linear(x, self.weight, ops.LINEAR_BF16, packed=self.weight_packed)
+            y = decode_linear(x, self.weight, ops.LINEAR_BF16, packed=self.weight_packed, fp8=self._fp8())
             if y is not None:
                 return y
         return F.linear(x, self.weight, self.bias)
@@ -400,12 +440,18 @@ def _use_wide(x: torch.Tensor, weight: torch.Tensor, mode: int, packed: torch.Te
 
 
 def decode_linear(x: torch.Tensor, weight: torch.Tensor, mode: int, out: torch.Tensor | None = None,
-                  packed: torch.Tensor | None = None):
+                  packed: torch.Tensor | None = None, fp8: tuple | None = None):
     """x [M, K] . weight[N, K]^T on a hand-written decode GEMM, or None when neither kernel takes the shape (the
     caller keeps the library GEMM). mode as in ops.linear_decode. `packed`: the module's tile-packed copy of
-    `weight` (LinearBase.pack_for_decode), streamed by the wide kernel instead of the row-major parameter."""
+    `weight` (LinearBase.pack_for_decode), streamed by the wide kernel instead of the row-major parameter. `fp8`: the
+    module's (e4m3 tile-packed weight, scales) — then nvl_linear_wide_fp8 takes every shape its plan covers (a shape
+    rule: no timing decides), and the rest falls through to the bf16 paths on the dequantised `weight`."""
     m, k = x.shape
     n = weight.shape[0]
+    if fp8 is not None:
+        plan = ops.linear_wide_fp8_plan(m, n, k, mode)
+        if plan is not None:
+            return ops.linear_wide_fp8(x, fp8[0], fp8[1], mode, out=out, workspace=_scratch(plan[1], x.device))
     if ops.linear_decode_splits(m, n, k, mode):
         if packed is not None:
             return ops.linear_decode(x, packed, mode, out=out, packed=True)
@@ -455,7 +501,7 @@ class MergedColumnParallelLinear(ColumnParallelLinear):
         epilogue (one launch, no [N, 2*inter] round trip)."""
         if (self.bias is None and len(self.output_sizes) == 2 and self.output_sizes[0] == self.output_sizes[1]
                 and _decode_sized(x)):
-            y = decode_linear(x, self.weight, ops.LINEAR_SILU, packed=self.weight_packed)
+            y = decode_linear(x, self.weight, ops.LINEAR_SILU, packed=self.weight_packed, fp8=self._fp8())
             if y is not None:
                 return y
         return ops.silu_mul(self.forward(x))
@@ -491,6 +537,12 @@ class QKVParallelLinear(ColumnParallelLinear):
                 and ops.decode_attention_takes_qkv_slabs(self.num_heads, self.num_kv_heads)):
             m, k = x.shape
             n = self.weight.shape[0]
+            if self.weight_fp8_packed is not None:                           # fp8 weights: the same hand-off, by the fp8 plan
+                plain = ops.linear_wide_fp8_plan(m, n, k, ops.LINEAR_BF16)
+                slabs = ops.linear_wide_fp8_plan(m, n, k, ops.LINEAR_PARTIAL) if plain else None
+                if plain and plain[0] > 1 and slabs and slabs[0] <= 8:
+                    return decode_linear(x, self.weight, ops.LINEAR_PARTIAL, fp8=self._fp8())
+                return self.forward(x)
             if not ops.linear_decode_splits(m, n, k, ops.LINEAR_BF16):       # (the skinny kernel never leaves slabs)
                 plain = ops.linear_wide_plan(m, n, k, ops.LINEAR_BF16) if k % 128 == 0 else None
                 slabs = ops.linear_wide_plan(m, n, k, ops.LINEAR_PARTIAL) if plain else None
@@ -535,7 +587,7 @@ class RowParallelLinear(LinearBase):
         n, k = self.weight.shape
         if self.tp_size == 1:
             if self.bias is None and _decode_sized(x):
-                y = decode_linear(x, self.weight, ops.LINEAR_PARTIAL, packed=self.weight_packed)
+                y = decode_linear(x, self.weight, ops.LINEAR_PARTIAL, packed=self.weight_packed, fp8=self._fp8())
                 if y is not None:
                     return y
             return self.forward(x)
@@ -544,7 +596,8 @@ class RowParallelLinear(LinearBase):
             # the GEMM writes its partial sums straight into this rank's shared comm region: the all-reduce kernel
             # then starts at its first flag instead of a copy-in phase
             buf = c.input_buffer(x.shape[0], n, x.device)
-            if not _decode_sized(x) or decode_linear(x, self.weight, ops.LINEAR_BF16, out=buf, packed=self.weight_packed) is None:
+            if not _decode_sized(x) or decode_linear(x, self.weight, ops.LINEAR_BF16, out=buf, packed=self.weight_packed,
+                                                          fp8=self._fp8()) is None:
                 torch.mm(x, self.weight.t(), out=buf)
             return PartialSum(buf)
         return self.forward(x)

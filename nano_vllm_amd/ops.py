@@ -32,6 +32,10 @@ SIGNATURES = {
     "nvl_linear_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                 c_void_p]),
     "nvl_pack_weight_tiles": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "nvl_linear_wide_fp8_plan": (c_int, [c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "nvl_linear_wide_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_size_t,
+                                    c_void_p]),
+    "nvl_pack_weight_tiles_fp8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "nvl_add_rmsnorm_splitk": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p]),
     "nvl_silu_mul": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
     "nvl_rope_neox": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
@@ -266,6 +270,58 @@ def linear_wide(x: torch.Tensor, weight: torch.Tensor, mode: int = LINEAR_BF16, 
     assert not ws_bytes or workspace.numel() * workspace.element_size() >= ws_bytes
     _check(lib().nvl_linear_wide(x.data_ptr(), weight.data_ptr(), out.data_ptr(), m, n, k, mode, 1 if packed else 0,
                                  workspace.data_ptr() if ws_bytes else None, ws_bytes, _stream()))
+    return out
+
+
+# ---- weight-only FP8 (W8A16) wide linears: e4m3 weights, fp32 scale per (16-row tile, 128-column k block) ---------
+_wide_fp8_cache: dict = {}
+
+
+def linear_wide_fp8_plan(m: int, n: int, k: int, mode: int) -> tuple[int, int] | None:
+    """(K splits, workspace bytes) of nvl_linear_wide_fp8's plan for this shape, or None when it is not covered."""
+    key = (m, n, k, mode)
+    if key not in _wide_fp8_cache:
+        splits, ws = ctypes.c_int(0), ctypes.c_size_t(0)
+        ok = lib().nvl_linear_wide_fp8_plan(m, n, k, mode, ctypes.byref(splits), ctypes.byref(ws))
+        _wide_fp8_cache[key] = (splits.value, ws.value) if ok else None
+    return _wide_fp8_cache[key]
+
+
+def pack_weight_tiles_fp8(w8: torch.Tensor) -> torch.Tensor:
+    """Tile-packed copy of a row-major [N, K] float8_e4m3fn weight (nvl_pack_weight_tiles_fp8): same shape and bytes,
+    stored as [N/16][K/64][64 lanes][16 bytes] — a wave load of nvl_linear_wide_fp8's weight stream is one contiguous KiB."""
+    _dev(w8, "w8")
+    assert w8.dim() == 2 and w8.is_contiguous() and w8.dtype == torch.float8_e4m3fn
+    n, k = w8.shape
+    packed = torch.empty_like(w8)
+    _check(lib().nvl_pack_weight_tiles_fp8(w8.data_ptr(), packed.data_ptr(), n, k, _stream()))
+    return packed
+
+
+def linear_wide_fp8(x: torch.Tensor, w8_packed: torch.Tensor, scales: torch.Tensor, mode: int = LINEAR_BF16,
+                    out: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """x [M, K] bf16 . (w8 o scales)^T: `w8_packed` the pack_weight_tiles_fp8() copy of the [N, K] e4m3 weight, `scales`
+    fp32 [N/16, K/128]. Modes, outputs and `workspace` as linear_wide."""
+    _dev(x, "x")
+    assert x.dim() == 2 and x.is_contiguous() and w8_packed.is_contiguous() and scales.is_contiguous()
+    assert x.dtype == torch.bfloat16 and w8_packed.dtype == torch.float8_e4m3fn and scales.dtype == torch.float32
+    m, k = x.shape
+    n = w8_packed.shape[0]
+    assert w8_packed.shape[1] == k and scales.shape == (n // 16, k // 128)
+    plan = linear_wide_fp8_plan(m, n, k, mode)
+    if plan is None:
+        raise NvlError(f"nvl_linear_wide_fp8 does not cover m={m} n={n} k={k} mode={mode}")
+    splits, ws_bytes = plan
+    if out is None:
+        if mode == LINEAR_PARTIAL:
+            out = torch.empty((splits, m, n), dtype=torch.float32, device=x.device)
+        else:
+            out = torch.empty((m, n // 2 if mode == LINEAR_SILU else n), dtype=torch.bfloat16, device=x.device)
+    if ws_bytes and workspace is None:
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    assert not ws_bytes or workspace.numel() * workspace.element_size() >= ws_bytes
+    _check(lib().nvl_linear_wide_fp8(x.data_ptr(), w8_packed.data_ptr(), scales.data_ptr(), out.data_ptr(), m, n, k, mode,
+                                     workspace.data_ptr() if ws_bytes else None, ws_bytes, _stream()))
     return out
 
 

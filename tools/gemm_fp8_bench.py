@@ -1,0 +1,106 @@
+"""nvl_linear_wide_fp8 against nvl_linear_wide on the bf16 tile-packed weight, same process, cold L2 / MALL before every
+sample (layers._time_cold), best of 5: every Qwen3-8B / 32B decode projection, full width and the TP = 8 per-rank shape,
+at 16 / 64 / 144 / 256 rows. Writes a JSON table (us, achieved weight GB/s, the two refitted terms of the time model).
+
+    python tools/gemm_fp8_bench.py [--out profiles/fp8_gemm_wide_vs_bf16.json] [--engine]
+
+--engine adds one engine-level pair: qwen3-8b dummy weights, 256 sequences, weight_dtype bf16 against fp8, LLM.generate.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from nano_vllm_amd import layers, ops  # noqa: E402
+
+MODELS = {"8b": (4096, 12288, 32, 8), "32b": (5120, 25600, 64, 8)}
+ROWS = (16, 64, 144, 256)
+
+
+def shapes():
+    for model, (hidden, inter, heads, kv) in MODELS.items():
+        for tp in (1, 8):
+            yield model, tp, "qkv", (heads + 2 * kv) * 128 // tp, hidden, ops.LINEAR_BF16
+            yield model, tp, "o", hidden, heads * 128 // tp, ops.LINEAR_PARTIAL
+            yield model, tp, "gate_up", 2 * inter // tp, hidden, ops.LINEAR_SILU
+            yield model, tp, "down", hidden, inter // tp, ops.LINEAR_PARTIAL
+
+
+def bench_gemms():
+    dev = torch.device("cuda")
+    rows = []
+    for model, tp, proj, n, k, mode in shapes():
+        w = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
+        wp = ops.pack_weight_tiles(w)
+        w8p = ops.pack_weight_tiles_fp8(w.to(torch.float8_e4m3fn))
+        sc = torch.ones(n // 16, k // 128, device=dev)
+        del w
+        for m in ROWS:
+            x = (torch.randn(m, k, device=dev) * 0.5).to(torch.bfloat16)
+            p16, p8 = ops.linear_wide_plan(m, n, k, mode), ops.linear_wide_fp8_plan(m, n, k, mode)
+            ws16 = torch.empty(max(p16[1], 16), dtype=torch.uint8, device=dev)
+            ws8 = torch.empty(max(p8[1], 16), dtype=torch.uint8, device=dev)
+            o16 = ops.linear_wide(x, wp, mode, workspace=ws16, packed=True)
+            o8 = ops.linear_wide_fp8(x, w8p, sc, mode, workspace=ws8)
+            t16 = layers._time_cold(lambda: ops.linear_wide(x, wp, mode, out=o16, workspace=ws16, packed=True), dev, 5) * 1e3
+            t8 = layers._time_cold(lambda: ops.linear_wide_fp8(x, w8p, sc, mode, out=o8, workspace=ws8), dev, 5) * 1e3
+            rows.append(dict(model=model, tp=tp, proj=proj, n=n, k=k, mode=mode, m=m, bf16_us=round(t16, 2), fp8_us=round(t8, 2),
+                             bf16_splits=p16[0], fp8_splits=p8[0], bf16_w_gbs=round(n * k * 2 / t16 / 1e3, 1),
+                             fp8_w_gbs=round(n * k / t8 / 1e3, 1), speedup=round(t16 / t8, 3)))
+            print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def refit(rows):
+    """T = W bytes per CU / a + x bytes per CU / b over the fp8 rows (256 CUs; x bytes per CU taken at 192 columns per
+    workgroup, the plan's wide form — rows whose plan took 96 columns are under-counted): least squares for 1/a, 1/b."""
+    a = torch.tensor([[r["n"] * r["k"] / 256.0, r["m"] * r["k"] * 2.0 * (r["n"] / 192.0) / 256.0] for r in rows], dtype=torch.float64)
+    t = torch.tensor([[r["fp8_us"]] for r in rows], dtype=torch.float64)
+    sol = torch.linalg.lstsq(a, t).solution.flatten().tolist()
+    return dict(w_gbs_per_cu=round(1e-3 / sol[0], 2) if sol[0] > 0 else None, x_gbs_per_cu=round(1e-3 / sol[1], 2) if sol[1] > 0 else None)
+
+
+def bench_engine():
+    from nano_vllm_amd import LLM, SamplingParams
+    from nano_vllm_amd.weights import write_synthetic_checkpoint
+    path = tempfile.mkdtemp(prefix="qwen3_8b_")
+    write_synthetic_checkpoint(path, "qwen3-8b", with_weights=False)
+    g = torch.Generator().manual_seed(0)
+    prompts = [torch.randint(0, 10000, (int(torch.randint(100, 1024, (1,), generator=g)),), generator=g).tolist() for _ in range(256)]
+    sp = SamplingParams(temperature=0.6, max_tokens=128, ignore_eos=True)
+    out = {}
+    for dt in ("bf16", "fp8"):
+        llm = LLM(path, dummy_weights=True, max_model_len=4096, max_num_seqs=256, weight_dtype=dt)
+        llm.generate(prompts[:8], SamplingParams(temperature=0.6, max_tokens=8, ignore_eos=True), use_tqdm=False)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        llm.generate(prompts, sp, use_tqdm=False)
+        torch.cuda.synchronize()
+        dtm = time.perf_counter() - t0
+        out[dt] = dict(seconds=round(dtm, 3), output_tok_s=round(256 * 128 / dtm, 1),
+                       packed_weight_bytes=llm.model_runner.packed_weight_bytes)
+        llm.exit()
+        del llm
+        torch.cuda.empty_cache()
+        print(json.dumps({dt: out[dt]}), flush=True)
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="profiles/fp8_gemm_wide_vs_bf16.json")
+    ap.add_argument("--engine", action="store_true")
+    args = ap.parse_args()
+    table = bench_gemms()
+    result = dict(gemm=table, refit_fp8=refit(table))
+    if args.engine:
+        result["engine_qwen3_8b_256seq"] = bench_engine()
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print(json.dumps(result["refit_fp8"]))
