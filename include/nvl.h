@@ -366,6 +366,25 @@ int nvl_sample(const void* logits, int64_t logits_row_stride,
  * reference's torch generator is consumed in batch order, layers/sampler.py:11: there the
  * tokens of a request change with its neighbours). */
 
+/* Top-k / top-p form of the sampler: per row, top_k int32 [batch] (<= 0 or >= vocab: off) and
+ * top_p fp32 [batch] (>= 1: off) truncate the distribution before the same race:
+ *   v_k = the k-th largest logit;  S_k = {i : l_i >= v_k}               (ties at v_k all kept)
+ *   w_i = exp((l_i - max) / T),  M(v) = sum of w_i over i in S_k with l_i >= v
+ *   v_p = the largest v with M(v) >= top_p * M(v_k)                     (ties at the cut all kept)
+ *   token = argmax over {i : l_i >= tau = max(v_k, v_p)} of l_i/T - log E_i, E as in nvl_sample.
+ * A row with both filters off, and every T == 0 row, returns nvl_sample's token bit for bit.
+ * A filter that asks for one column (top_k == 1, or a top_p that one maximal column already
+ * holds) makes the row greedy: the lowest index among the maxima, not a draw between them.
+ * One launch, one workgroup per row: an exact radix select over the 65,536 possible bf16 values
+ * (integer histograms in LDS; masses are 2^40 fixed point, so tau does not depend on the order
+ * of the atomics), the row held in registers up to 155,648 columns. `tau` (optional, may be
+ * NULL): fp32 [batch], receives each row's cut (-inf: nothing was cut). No workspace. */
+int nvl_sample_topk_topp(const void* logits, int64_t logits_row_stride,
+                         const float* temperatures, const int32_t* top_k, const float* top_p,
+                         int64_t* out, float* tau, int64_t batch, int64_t vocab,
+                         uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                         const uint64_t* row_keys, void* stream);
+
 /* Vocab-parallel form of the sampler (the reference gathers every rank's [batch, vocab/tp]
  * logits on rank 0, layers/embed_head.py:62-65, and samples there; here each rank reduces ITS
  * shard to one {key, index} pair per row and only those 8 bytes per row travel):

@@ -5,6 +5,9 @@ sampling_params.py:5-11) so callers of `nanovllm.LLM(model, **kwargs)` switch ov
 Extensions (all optional, behaviour-neutral when unset):
   * SamplingParams.temperature == 0 selects greedy decoding (the reference forbids it; the
     parity harness needs it — SURVEY.md §0-7).
+  * SamplingParams.top_k / top_p truncate the distribution before the draw (top-k first, then top-p renormalised over
+    the survivors, ties at a cut kept); 0 / -1 and 1.0 switch them off. Single GPU only: tensor_parallel_size > 1
+    refuses such a request.
   * Config.seed seeds the counter-based sampler RNG.
   * Config.dummy_weights = True initialises random weights on device instead of reading
     *.safetensors (no 8B/32B checkpoints exist offline).
@@ -26,10 +29,14 @@ class SamplingParams:
     temperature: float = 1.0
     max_tokens: int = 64
     ignore_eos: bool = False
+    top_k: int = 0                # 0 or -1: off
+    top_p: float = 1.0            # 1.0: off
 
     def __post_init__(self):
         assert self.temperature == 0 or self.temperature > 1e-10, "temperature must be 0 (greedy) or > 1e-10"
         assert self.max_tokens >= 1
+        assert self.top_k >= -1, "top_k must be >= -1 (0 or -1: off)"
+        assert 0 < self.top_p <= 1, "top_p must be in (0, 1]"
 
 
 @dataclass(slots=True)

@@ -106,6 +106,10 @@ class LLMEngine:
         assert len(prompt) + sampling_params.max_tokens <= self.config.max_model_len, (
             f"prompt ({len(prompt)} tokens) + max_tokens ({sampling_params.max_tokens}) exceeds "
             f"max_model_len ({self.config.max_model_len})")
+        # the top-k / top-p selection needs a row's whole vocabulary; under TP every rank holds a shard of it
+        if self.config.tensor_parallel_size > 1 and (sampling_params.top_k > 0 or sampling_params.top_p < 1):
+            raise ValueError("top_k / top_p are not supported with tensor_parallel_size > 1 (the vocabulary is sharded "
+                             "across the ranks): run the request without them or on a single GPU")
         return prompt
 
     def _new_sequence(self, prompt: list[int], sampling_params: SamplingParams) -> Sequence:

@@ -440,12 +440,13 @@ class ModelRunner:
         self.dstage = _Stage([
             ("ids", np.int64, (mb,)), ("pos", np.int64, (mb,)), ("rng", np.uint64, (2,)), ("rkey", np.int64, (mb,)),
             ("slots", np.int32, (mb,)), ("ctx", np.int32, (mb,)), ("temps", np.float32, (mb,)),
-            ("src", np.int32, (mb,)), ("shp", np.int32, (1 + mb,)), ("bt", np.int32, (mb, w)),
+            ("topk", np.int32, (mb,)), ("topp", np.float32, (mb,)), ("src", np.int32, (mb,)), ("shp", np.int32, (1 + mb,)), ("bt", np.int32, (mb, w)),
         ], self.device, host_copies=2)
         for image in self.dstage.nps:
             image["slots"][:] = -1
             image["bt"][:] = -1
             image["src"][:] = -1
+            image["topp"][:] = 1.0
         self.dstage.upload()
         # per pinned image: (seq id, #blocks, allocation stamp) per decode row whose block-table row is current
         self._row_keys = [np.full((mb, 3), -1, dtype=np.int64) for _ in self.dstage.nps]
@@ -455,7 +456,8 @@ class ModelRunner:
         self.pstage = _Stage([
             ("ids", np.int64, (nt,)), ("pos", np.int64, (nt,)), ("rng", np.uint64, (2,)), ("rkey", np.int64, (ns,)),
             ("slots", np.int32, (nt,)), ("cu_q", np.int32, (ns + 1,)), ("cu_k", np.int32, (ns + 1,)),
-            ("temps", np.float32, (ns,)), ("bt", np.int32, (ns, w)),
+            ("temps", np.float32, (ns,)), ("topk", np.int32, (ns,)), ("topp", np.float32, (ns,)),
+            ("bt", np.int32, (ns, w)),
         ], self.device)
         self.step_count = 0
         self.share_prefix = False            # (decided below, once the device side exists)
@@ -495,9 +497,11 @@ class ModelRunner:
                                                                       self.block_size))
         self.share_prefix_min_bytes = float(os.environ.get("NVL_SHARED_PREFIX_MIN_MB", "100")) * 1e6
         self.decode_plan_px = torch.zeros(ops.decode_plan_bytes(), dtype=torch.uint8, device=self.device)
-        self.graphs_px: dict[tuple, torch.cuda.CUDAGraph] = {}      # (bucket, group slots) -> graph with the pass
+        self.graphs_px: dict[tuple, torch.cuda.CUDAGraph] = {}      # (bucket, group slots, filtered) -> variant graph
         self.prefix_steps = 0                # decode steps that ran the shared-prefix pass (reporting)
         self.prefix_multi_steps = 0          # ... with more than one shared prefix in the batch
+        self.filtered_steps = 0              # decode steps sampled by the top-k / top-p kernel (some row had a filter on)
+        self.filtered_graph_steps = 0        # ... that were a graph replay
         self._step_done = [torch.cuda.Event(), torch.cuda.Event()]
         # TP with the xGMI P2P collectives: every spin of those kernels is bounded, and a timeout is LATCHED in the shared
         # flag region while the step carries on with an invalid sum. The last node of every step (prefill and decode,
@@ -587,6 +591,7 @@ class ModelRunner:
             else:                                              # warm-up: no cache, nothing to store
                 have_slots = False
             st["temps"][i] = seq.temperature
+            st["topk"][i], st["topp"][i] = seq.top_k, seq.top_p
             st["rkey"][i] = seq.rng_key | (end << 32)          # the draw of the token that will sit at position `end`
             n += lq
         ns = len(seqs)
@@ -625,6 +630,8 @@ class ModelRunner:
         last_blk = np.fromiter((s.block_table[-1] for s in seqs), dtype=np.int64, count=n)
         st["slots"][:n] = last_blk * bs + (lens - 1) % bs
         st["temps"][:n] = [s.temperature for s in seqs]
+        st["topk"][:n] = [s.top_k for s in seqs]
+        st["topp"][:n] = [s.top_p for s in seqs]
         # block tables: rewrite a row only when its (sequence, #blocks, allocation stamp) changed in THIS image.
         # The stamp matters: a preempted sequence that is prefilled again may come back to the same row with the
         # same number of blocks but other block ids (kv_blocks.BlockManager.allocate).
@@ -679,20 +686,29 @@ class ModelRunner:
         self.step_count += 1
         st.np["rng"][0] = 0
 
-    def _sample(self, hidden, temps, out, rng, sampler, rkey=None):
+    @staticmethod
+    def _filtered(image: dict, n: int) -> bool:
+        """Does any of the first n staged rows have a top-k / top-p filter on? (Every rank reads the same image.)"""
+        return bool((image["topk"][:n] > 0).any() or (image["topp"][:n] < 1).any())
+
+    def _sample(self, hidden, temps, out, rng, sampler, rkey=None, filters=None):
         """lm_head + sampler on the current stream; TP > 1: every rank samples its vocabulary shard and the
-        per-row winners are merged on every rank (no [B, V] gather, embed_head.py:62-65)."""
+        per-row winners are merged on every rank (no [B, V] gather, embed_head.py:62-65). `filters`: the step's
+        (top_k, top_p) rows when some row has a filter on — the top-k / top-p kernel samples the whole step."""
         col0 = self.rank * self.geo["vocab_per_rank"]
         if self.world_size == 1:
-            sampler(self.model.compute_logits(hidden), temps, out=out, offset_dev=rng, row_keys=rkey)
+            top_k, top_p = filters if filters is not None else (None, None)
+            sampler(self.model.compute_logits(hidden), temps, out=out, offset_dev=rng, row_keys=rkey, top_k=top_k, top_p=top_p)
         else:
+            assert filters is None, "top-k / top-p needs the whole vocabulary row: requests with a filter are refused at TP > 1"
             logits = self.model.compute_logits_shard(hidden)
             sampler.forward_shard(logits, temps, col0, out, offset_dev=rng, row_keys=rkey)
 
-    def _decode_rows(self, r0: int, r1: int, ws, sampler, plan=None, prefix: int = 0):
+    def _decode_rows(self, r0: int, r1: int, ws, sampler, plan=None, prefix: int = 0, filtered: bool = False):
         """Decode forward for rows [r0, r1) of the static device buffers, on the current stream. `prefix` > 0: the plan
         carries the step's shared-prefix groups (staged as `shp`), the attention launches run the shared pass with that
-        many group slots per pack (1: one shared prefix in the step; MAX_PREFIX_GROUPS: several)."""
+        many group slots per pack (1: one shared prefix in the step; MAX_PREFIX_GROUPS: several). `filtered`: the sampler
+        node is the top-k / top-p kernel, reading the rows' staged filters."""
         t = self.dstage.t
         assert not prefix or r0 == 0           # (the member flags are staged per row of the whole batch)
         if plan is not None:
@@ -703,7 +719,8 @@ class ModelRunner:
                     block_tables=t["bt"][r0:r1], decode_workspace=ws, max_context=self.config.max_model_len,
                     decode_plan=plan, shared_prefix=bool(prefix) and plan is not None)
         hidden = self.model(t["ids"][r0:r1], t["pos"][r0:r1])
-        self._sample(hidden, t["temps"][r0:r1], self.tokens_dev[r0:r1], t["rng"][:1], sampler, t["rkey"][r0:r1])
+        self._sample(hidden, t["temps"][r0:r1], self.tokens_dev[r0:r1], t["rng"][:1], sampler, t["rkey"][r0:r1],
+                     (t["topk"][r0:r1], t["topp"][r0:r1]) if filtered else None)
         reset_context()
         self._collect_comm_status()
 
@@ -720,7 +737,7 @@ class ModelRunner:
                                "collectives over the process group instead")
 
     @torch.inference_mode()
-    def _forward_decode(self, bs: int, prefix: int = 0):
+    def _forward_decode(self, bs: int, prefix: int = 0, filtered: bool = False):
         """Decode forward on the static device buffers (captured per bucket, or run eagerly): layers + lm_head
         + sampler, at any TP degree (the reference captures the layers only and runs lm_head, the logits
         gather and the sampler eagerly, model_runner.py:212,218). (A micro-batched form — two half-batch chains on
@@ -730,7 +747,7 @@ class ModelRunner:
         t = self.dstage.t
         ops.feed_tokens(t["ids"][:bs], t["src"][:bs], self.tokens_dev)
         plan = (self.decode_plan_px if prefix else self.decode_plan) if self.use_plan else None
-        self._decode_rows(0, bs, self.decode_ws, self.sampler, plan, prefix)
+        self._decode_rows(0, bs, self.decode_ws, self.sampler, plan, prefix, filtered)
 
     @torch.inference_mode()
     def _launch_decode(self, n: int) -> None:
@@ -743,19 +760,26 @@ class ModelRunner:
             prefix = 1 if int(self.dstage.np["shp"][1:1 + n].max()) <= 1 else MAX_PREFIX_GROUPS
         self.prefix_steps += int(prefix > 0)
         self.prefix_multi_steps += int(prefix > 1)
-        key = (bucket, prefix)
-        if bucket is not None and prefix and key not in self.graphs_px and not self._capture_prefix_graph(bucket, prefix):
-            # the capture failed (single rank only; _capture_prefix_graph raises under TP): this step replays the bucket's
-            # plain graph, whose plan is built without the staged groups
+        # a step with a top-k / top-p filter in any row swaps the sampler node; every other step launches what it always did
+        filtered = self._filtered(self.dstage.np, n)
+        self.filtered_steps += int(filtered)
+        key = (bucket, prefix, filtered)
+        if bucket is not None and prefix and key not in self.graphs_px and not self._capture_variant_graph(*key):
+            # the capture failed (single rank only; _capture_variant_graph raises under TP): this step runs without the
+            # pass, on a plan built without the staged groups
             self.prefix_steps -= 1
             self.prefix_multi_steps -= int(prefix > 1)
             prefix = 0
-        if bucket is not None and prefix:
+            key = (bucket, 0, filtered)
+        if bucket is not None and filtered and key not in self.graphs_px and not self._capture_variant_graph(*key):
+            bucket = None                    # no graph with the filtering sampler for this bucket: the step runs eagerly
+        if bucket is not None and (prefix or filtered):
             self.graphs_px[key].replay()
+            self.filtered_graph_steps += int(filtered)
         elif bucket is not None:
             self.graphs[bucket].replay()
         else:
-            self._forward_decode(n, prefix)
+            self._forward_decode(n, prefix, filtered)
         host = self.tokens_host if self._flight_parity == 0 else self.tokens_host_b
         done = self._step_done[self._flight_parity]
         if self.rank == 0:
@@ -809,7 +833,8 @@ class ModelRunner:
         set_context(True, t["cu_q"][:ns + 1], t["cu_k"][:ns + 1], info["max_q"], info["max_k"],
                     t["slots"][:n] if info["have_slots"] else None, None, t["bt"][:ns] if info["paged"] else None)
         hidden = self.model(t["ids"][:n], t["pos"][:n])
-        self._sample(hidden, t["temps"][:ns], self.tokens_dev[:ns], t["rng"][:1], self.sampler, t["rkey"][:ns])
+        filters = (t["topk"][:ns], t["topp"][:ns]) if self._filtered(self.pstage.np, ns) else None
+        self._sample(hidden, t["temps"][:ns], self.tokens_dev[:ns], t["rng"][:1], self.sampler, t["rkey"][:ns], filters)
         reset_context()
         self._collect_comm_status()
 
@@ -861,15 +886,22 @@ class ModelRunner:
             # of the plain kernel (attn_decode.hip), i.e. during the eager warm-ups above, never inside a capture.
             self._forward_decode(self.graph_bs[-1], prefix=1)
             torch.cuda.synchronize()
-            self._capture_prefix_graph(self.graph_bs[-1], 1)
+            self._capture_variant_graph(self.graph_bs[-1], 1)
+        if self.world_size == 1:
+            # first launch of the top-k / top-p kernel outside any capture (one 8-column row, before any step has run); its
+            # graphs are captured when a step first carries a filter
+            t = self.dstage.t
+            ops.sample_topk_topp(torch.zeros(1, 8, dtype=torch.bfloat16, device=self.device), t["temps"][:1],
+                                 t["topk"][:1], t["topp"][:1], 0, 0, out=self.tokens_dev[:1])
         torch.cuda.synchronize()
         from .. import layers
         layers.release_tuning_scratch()                 # the decode-GEMM choices of every bucket are made by now
 
     @torch.inference_mode()
-    def _capture_prefix_graph(self, bs: int, groups: int = 1) -> bool:
-        """The decode graph of bucket `bs` WITH the shared-prefix attention pass, captured the first time a step wants
-        it (most workloads never do; the largest bucket's is captured at start-up). No warm-up run on the serving path:
+    def _capture_variant_graph(self, bs: int, groups: int = 0, filtered: bool = False) -> bool:
+        """A second decode graph of bucket `bs`: WITH the shared-prefix attention pass (`groups` > 0 group slots) and / or
+        with the top-k / top-p kernel as its sampler node (`filtered`), captured the first time a step wants
+        it (most workloads never do; the largest bucket's prefix graph is captured at start-up). No warm-up run on the serving path:
         the static buffers hold a real step's inputs by now, every choice the launches make was made when the bucket's
         plain graph was captured, and the allocations come out of the plain graphs' pool. Every rank captures at the same
         step (the decision is read from the staged image). Returns False when the capture failed on a single-rank
@@ -879,13 +911,16 @@ class ModelRunner:
         graph = torch.cuda.CUDAGraph()
         try:
             with torch.cuda.graph(graph, self.graph_pool):
-                self._forward_decode(bs, prefix=groups)
+                self._forward_decode(bs, prefix=groups, filtered=filtered)
         except Exception as e:      # OOM of the pool's headroom, a launch refused inside the capture
             if self.world_size > 1:
                 raise
             import warnings
-            warnings.warn(f"shared-prefix graph of bucket {bs} could not be captured ({e!r}); the pass is off")
-            self.share_prefix = False
+            if groups:
+                warnings.warn(f"shared-prefix graph of bucket {bs} could not be captured ({e!r}); the pass is off")
+                self.share_prefix = False
+            else:
+                warnings.warn(f"top-k / top-p graph of bucket {bs} could not be captured ({e!r}); the step runs eagerly")
             return False
-        self.graphs_px[(bs, groups)] = graph
+        self.graphs_px[(bs, groups, filtered)] = graph
         return True

@@ -181,10 +181,13 @@ class Sampler(nn.Module):
         self.capture: list | None = None        # tests: every step's logits (fp32, host) are appended here
 
     def forward(self, logits: torch.Tensor, temperatures: torch.Tensor, out: torch.Tensor | None = None,
-                offset_dev: torch.Tensor | None = None, row_keys: torch.Tensor | None = None) -> torch.Tensor:
+                offset_dev: torch.Tensor | None = None, row_keys: torch.Tensor | None = None,
+                top_k: torch.Tensor | None = None, top_p: torch.Tensor | None = None) -> torch.Tensor:
         """`row_keys` (int64 [B]: request ordinal | position << 32, extension): each row's draw is keyed by its
         sequence and position instead of by its row in this batch (the reference's generator is consumed in batch
-        order, sampler.py:11)."""
+        order, sampler.py:11). `top_k` (int32 [B]) / `top_p` (fp32 [B]), extension: given both, the step goes through
+        the top-k / top-p kernel (ops.sample_topk_topp); rows whose filters are off draw as without them."""
+        assert (top_k is None) == (top_p is None), "top_k and top_p come together (off values: 0 and 1.0)"
         b = logits.shape[0]
         need = ops.sample_workspace_bytes(max(b, 512))
         if self._ws is None or self._ws.numel() < need or self._ws.device != logits.device:
@@ -195,6 +198,9 @@ class Sampler(nn.Module):
         self.calls += 1
         if self.capture is not None:
             self.capture.append(logits.float().cpu())
+        if top_k is not None:
+            return ops.sample_topk_topp(logits, temperatures, top_k, top_p, self.seed, offset, out=out,
+                                        offset_dev=offset_dev, row_keys=row_keys)
         return ops.sample(logits, temperatures, self.seed, offset, self._ws, out=out, offset_dev=offset_dev,
                           row_keys=row_keys)
 

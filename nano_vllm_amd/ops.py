@@ -63,6 +63,8 @@ SIGNATURES = {
     "nvl_sample_shard": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_uint64, c_uint64,
                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nvl_sample_merge": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p]),
+    "nvl_sample_topk_topp": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "nvl_feed_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "nvl_allreduce_create": (c_int, [c_int, c_int, c_int64, ctypes.POINTER(c_void_p)]),
     "nvl_allreduce_uid": (c_int, [c_void_p, c_void_p]),
@@ -549,6 +551,34 @@ def sample(logits: torch.Tensor, temperatures: torch.Tensor, seed: int, offset: 
                             seed & 0xFFFFFFFFFFFFFFFF, offset & 0xFFFFFFFFFFFFFFFF,
                             offset_dev.data_ptr() if offset_dev is not None else None, _keys_ptr(row_keys, b),
                             workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()))
+    return out
+
+
+def sample_topk_topp(logits: torch.Tensor, temperatures: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                     seed: int, offset: int, out: torch.Tensor | None = None, tau: torch.Tensor | None = None,
+                     offset_dev: torch.Tensor | None = None, row_keys: torch.Tensor | None = None) -> torch.Tensor:
+    """`sample` with a per-row top-k / top-p filter: top_k int32 [B] (<= 0 or >= V: off), top_p fp32 [B] (>= 1: off).
+    A row keeps the columns l >= max(v_k, v_p) — v_k the k-th largest logit, v_p the largest value at which the mass of
+    exp((l - max) / T) over the top-k survivors reaches top_p of their total; ties at the cut are kept — and draws the
+    same race as `sample` over them: a row with both filters off (or T == 0) returns `sample`'s token bit for bit.
+    `tau` (optional, fp32 [B]) receives the row's cut max(v_k, v_p), -inf for an unfiltered row."""
+    _dev(logits, "logits")
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype == torch.bfloat16
+    assert temperatures.dtype == torch.float32
+    b, vocab = logits.shape
+    for name, t, dt in (("top_k", top_k, torch.int32), ("top_p", top_p, torch.float32)):
+        assert t.dtype == dt and t.dim() == 1 and t.is_contiguous() and t.numel() >= b and t.device == logits.device, \
+            f"{name}: want a contiguous {dt} [B] tensor on the logits' device"
+    if tau is not None:
+        assert tau.dtype == torch.float32 and tau.is_contiguous() and tau.numel() >= b and tau.device == logits.device
+    if out is None:
+        out = torch.empty(b, dtype=torch.int64, device=logits.device)
+    assert out.dtype == torch.int64 and out.numel() >= b
+    _check(lib().nvl_sample_topk_topp(logits.data_ptr(), logits.stride(0), temperatures.data_ptr(), top_k.data_ptr(),
+                                      top_p.data_ptr(), out.data_ptr(), tau.data_ptr() if tau is not None else None, b,
+                                      vocab, seed & 0xFFFFFFFFFFFFFFFF, offset & 0xFFFFFFFFFFFFFFFF,
+                                      offset_dev.data_ptr() if offset_dev is not None else None, _keys_ptr(row_keys, b),
+                                      _stream()))
     return out
 
 
