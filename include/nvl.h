@@ -164,6 +164,40 @@ int nvl_add_rmsnorm_splitk(const float* partials, int splits, void* residual,
                            const void* weight, void* y,
                            int64_t rows, int hidden, float eps, void* stream);
 
+/* ---- Sparse mixture-of-experts feed-forward block (Qwen3-MoE) ----------------------------------
+ * The `qwen3_moe` half of the family (Qwen3-30B-A3B, Qwen3-235B-A22B; not in the reference, which ships the dense
+ * models/qwen3.py only): per token, a router picks top_k of E experts, each a gate|up -> SiLU * mul -> down MLP of
+ * width `inter`, and the expert outputs are summed with the routing weights. Routing and the expert computation
+ * are separate calls (the experts run on ANY ids / weights), every grid depends on the host-known shapes only,
+ * nothing is combined with atomics: results are bit-identical from run to run. csrc/moe.hip has the decomposition.
+ *   nvl_moe_route: logit_e = fp32 sum of the bf16 products x[t] . router_w[e]; p = fp32 softmax over all E;
+ *     topk_ids[t] = the top_k largest p in descending order, ties to the LOWER expert index; topk_w[t, j] =
+ *     p / (sum of the selected p) if norm_topk_prob, else p. x [m, hidden] bf16, router_w [E, hidden] bf16,
+ *     topk_ids int32 [m, top_k], topk_w fp32 [m, top_k]. E <= 256, top_k <= 8, top_k <= E, hidden % 128 == 0,
+ *     hidden <= 4096 (the x row is held in registers; Qwen3-235B-A22B is 4096).
+ *   nvl_moe_plan: stable counting sort of the m * top_k (token, slot) pairs by expert (pair order inside an
+ *     expert) into `workspace`: per-expert offsets [E + 1], the sorted pair list, every pair's sorted position,
+ *     and the list of ROW BLOCKS (expert, first sorted row, rows <= 128), padded with empty blocks to its static
+ *     bound floor(m * top_k / 128) + min(E, m * top_k). An id outside [0, E) contributes nothing.
+ *   nvl_moe_experts: consumes the plan made for the SAME (topk_ids, m, E, top_k) in the same workspace:
+ *       h[pair]  = bf16( silu(bf16(x[t] . Wgate_e)) * bf16(x[t] . Wup_e) )        (nvl_linear_decode mode 1's rounding)
+ *       y[pair]  = h[pair] . Wdown_e                                               fp32
+ *       out[t]   = bf16( sum over j = 0 .. top_k - 1, in that order, of topk_w[t, j] * y[pair (t, j)] )   fp32 sum
+ *     x [m, hidden] bf16; w_gate_up [E, 2 * inter, hidden] (gate rows, then up rows); w_down [E, hidden, inter];
+ *     out [m, hidden] bf16. weight_layout 0: row-major parameters; 1: the nvl_pack_weight_tiles copies of the
+ *     stacked [E * n, k] matrices (n % 16 == 0: no tile straddles two experts). hidden % 128 == 0, inter % 128 == 0.
+ *   nvl_moe_workspace_bytes: bytes a workspace needs for calls of up to max_tokens rows (pure host code, monotone
+ *     in max_tokens; 0 for shapes outside the limits above). A call with more rows than its workspace holds is
+ *     NVL_EINVAL; the workspace is 256-byte aligned and needs no initialisation. */
+size_t nvl_moe_workspace_bytes(int64_t max_tokens, int hidden, int inter, int E, int top_k);
+int nvl_moe_route(const void* x, const void* router_w, int32_t* topk_ids, float* topk_w, int64_t m,
+                  int hidden, int E, int top_k, int norm_topk_prob, void* stream);
+int nvl_moe_plan(const int32_t* topk_ids, int64_t m, int E, int top_k, void* workspace,
+                 size_t workspace_bytes, void* stream);
+int nvl_moe_experts(const void* x, const void* w_gate_up, const void* w_down, const int32_t* topk_ids,
+                    const float* topk_w, void* out, int64_t m, int hidden, int inter, int E, int top_k,
+                    int weight_layout, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Rotary embedding -----------------------------------------------------
  * Replaces RotaryEmbedding.forward / apply_rotary_emb
  * (layers/rotary_embedding.py:6-14, 37-48): neox (half-split) rotation from a

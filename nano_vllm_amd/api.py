@@ -69,10 +69,35 @@ class Config:
         assert self.max_num_batched_tokens >= 1 and self.max_num_seqs >= 1
         assert self.kv_cache_dtype in ("bf16", "fp8"), "kv_cache_dtype must be 'bf16' or 'fp8'"
         assert self.weight_dtype in ("bf16", "fp8"), "weight_dtype must be 'bf16' or 'fp8'"
+        check_moe_scope(self.hf_config, self.tensor_parallel_size, self.weight_dtype)
+
+
+def check_moe_scope(hf_config, tp: int = 1, weight_dtype: str = "bf16") -> None:
+    """A `qwen3_moe` config is served on one GPU with bf16 experts, every layer sparse, no shared expert; anything else
+    is refused here, at load, rather than computed wrongly."""
+    if getattr(hf_config, "model_type", "qwen3") != "qwen3_moe":
+        return
+    if tp != 1:
+        raise ValueError("qwen3_moe: tensor_parallel_size > 1 is not supported (the expert kernels are single-GPU)")
+    if weight_dtype != "bf16":
+        raise ValueError("qwen3_moe: weight_dtype='fp8' is not supported (expert weights stay bf16)")
+    if getattr(hf_config, "decoder_sparse_step", 1) != 1 or list(getattr(hf_config, "mlp_only_layers", None) or []):
+        raise ValueError("qwen3_moe: decoder_sparse_step != 1 / mlp_only_layers are not supported (every layer is sparse)")
+    if (getattr(hf_config, "shared_expert_intermediate_size", 0) or getattr(hf_config, "n_shared_experts", 0)
+            or getattr(hf_config, "num_shared_experts", 0)):
+        raise ValueError("qwen3_moe: a shared expert is not supported")
+    e, k = hf_config.num_experts, hf_config.num_experts_per_tok
+    if not (1 <= k <= 8 and k <= e <= 256 and hf_config.hidden_size % 128 == 0 and hf_config.hidden_size <= 4096
+            and hf_config.moe_intermediate_size % 128 == 0):
+        raise ValueError(f"qwen3_moe: num_experts={e} (<= 256), num_experts_per_tok={k} (<= 8), hidden_size (<= 4096) and "
+                         "moe_intermediate_size (multiples of 128) are outside the expert kernels' range")
 
 
 def model_geometry(hf_config, tp: int = 1) -> dict:
     """Per-rank shapes of a Qwen3-family config (models/qwen3.py:29-39)."""
+    moe = getattr(hf_config, "model_type", "qwen3") == "qwen3_moe"
+    if moe:
+        check_moe_scope(hf_config, tp)
     heads = hf_config.num_attention_heads
     kv_heads = hf_config.num_key_value_heads
     head_dim = getattr(hf_config, "head_dim", None) or hf_config.hidden_size // heads
@@ -91,4 +116,8 @@ def model_geometry(hf_config, tp: int = 1) -> dict:
         head_dim=head_dim, inter=hf_config.intermediate_size // tp, vocab=hf_config.vocab_size,
         vocab_per_rank=hf_config.vocab_size // tp, eps=hf_config.rms_norm_eps, rope_theta=float(rope_theta),
         max_pos=hf_config.max_position_embeddings, tie=bool(getattr(hf_config, "tie_word_embeddings", False)),
-        qk_norm=not getattr(hf_config, "attention_bias", True), dtype=dtype)    # (default as models/qwen3.py:133)
+        qk_norm=not getattr(hf_config, "attention_bias", True), dtype=dtype,    # (default as models/qwen3.py:133)
+        # qwen3_moe: experts per layer, experts per token, expert width, renormalised routing weights (0 / False: dense)
+        num_experts=hf_config.num_experts if moe else 0, top_k=hf_config.num_experts_per_tok if moe else 0,
+        moe_inter=hf_config.moe_intermediate_size if moe else 0,
+        norm_topk_prob=bool(getattr(hf_config, "norm_topk_prob", False)) if moe else False)

@@ -37,7 +37,7 @@ from .. import ops
 from ..api import Config, model_geometry
 from ..attn_meta import get_context, reset_context, set_context
 from ..layers import Sampler
-from ..qwen3 import Qwen3ForCausalLM
+from ..qwen3 import Qwen3ForCausalLM, Qwen3MoeForCausalLM, Qwen3MoeSparseBlock
 from ..weights import init_dummy_weights, load_model
 from .seq import Sequence
 
@@ -312,11 +312,18 @@ class ModelRunner:
         torch.set_default_dtype(dtype)
         torch.set_default_device(self.device)
         try:
-            self.model = Qwen3ForCausalLM(hf)
+            model_cls = Qwen3MoeForCausalLM if self.geo["num_experts"] else Qwen3ForCausalLM    # hf.model_type: qwen3_moe / qwen3
+            self.model = model_cls(hf)
             if config.dummy_weights:
                 init_dummy_weights(self.model, hf, config.seed)
             else:
                 load_model(self.model, config.model)
+            self.moe_workspace_bytes = 0
+            if self.geo["num_experts"]:
+                # the MoE blocks' workspace: once, here — before the warm-up measures peak memory and the KV pool is
+                # sized from what is left, and never inside a graph capture. Prefills above the cap run in chunks.
+                cap = min(config.max_num_batched_tokens, int(os.environ.get("NVL_MOE_MAX_TOKENS", "2048")))
+                self.moe_workspace_bytes = self.model.allocate_moe_workspace(cap)
             # tile-packed copies of the deep-K projections for the decode GEMM (before the KV pool is sized from what
             # is left: a second copy of those weights is the price of a 4x cheaper weight stream per CU)
             self.packed_weight_bytes, self.packed_weight_skipped = self._pack_weights()
@@ -355,6 +362,12 @@ class ModelRunner:
         budget = min(float(os.environ.get("NVL_PACKED_BUDGET_FRAC", "0.25")) * total, 0.5 * free)
         used = skipped = 0
         for m in self.model.modules():
+            if isinstance(m, Qwen3MoeSparseBlock):       # the stacked expert matrices, under the same budget
+                got = m.pack_for_decode(budget - used)
+                if got < 0:
+                    skipped += 1
+                else:
+                    used += got
             if isinstance(m, (LinearBase, ParallelLMHead)):
                 if isinstance(m, LinearBase):      # (lm_head and embedding stay bf16, as in the published FP8 checkpoints)
                     got = m.pack_for_decode(budget - used, weight_dtype=self.config.weight_dtype)

@@ -38,6 +38,11 @@ SIGNATURES = {
     "nvl_pack_weight_tiles_fp8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "nvl_add_rmsnorm_splitk": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p]),
     "nvl_silu_mul": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    "nvl_moe_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    "nvl_moe_route": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "nvl_moe_plan": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "nvl_moe_experts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "nvl_rope_neox": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "nvl_store_kvcache": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64,
                                   c_int, c_void_p]),
@@ -340,6 +345,63 @@ def add_rmsnorm_splitk(partials: torch.Tensor, residual: torch.Tensor, weight: t
                                         m, h, eps, _stream()))
     return out
 
+
+
+# ---- sparse mixture-of-experts block (Qwen3-MoE): route -> plan -> experts -------------------------------------------
+def moe_workspace_bytes(max_tokens: int, hidden: int, inter: int, num_experts: int, top_k: int) -> int:
+    """Bytes of the workspace that serves calls of up to `max_tokens` rows (host code; raises on an unsupported shape)."""
+    n = lib().nvl_moe_workspace_bytes(max_tokens, hidden, inter, num_experts, top_k)
+    if n == 0:
+        raise NvlError(f"nvl_moe: unsupported shape max_tokens={max_tokens} hidden={hidden} inter={inter} "
+                       f"E={num_experts} top_k={top_k} (hidden, inter % 128 == 0; E <= 256; top_k <= 8, <= E)")
+    return n
+
+
+def moe_route(x: torch.Tensor, router_w: torch.Tensor, top_k: int, norm_topk_prob: bool,
+              ids: torch.Tensor | None = None, weights: torch.Tensor | None = None):
+    """x [M, H] bf16, router_w [E, H] bf16 -> (ids int32 [M, top_k], weights fp32 [M, top_k]): top_k of the fp32 softmax
+    over all E experts, descending, ties to the lower index; weights renormalised over the selection if `norm_topk_prob`."""
+    _dev(x, "x")
+    assert x.dim() == 2 and x.is_contiguous() and router_w.is_contiguous()
+    assert x.dtype == torch.bfloat16 and router_w.dtype == torch.bfloat16 and router_w.shape[1] == x.shape[1]
+    m, hidden = x.shape
+    if ids is None:
+        ids = torch.empty((m, top_k), dtype=torch.int32, device=x.device)
+    if weights is None:
+        weights = torch.empty((m, top_k), dtype=torch.float32, device=x.device)
+    assert ids.dtype == torch.int32 and weights.dtype == torch.float32 and ids.numel() == m * top_k == weights.numel()
+    _check(lib().nvl_moe_route(x.data_ptr(), router_w.data_ptr(), ids.data_ptr(), weights.data_ptr(), m, hidden,
+                               router_w.shape[0], top_k, 1 if norm_topk_prob else 0, _stream()))
+    return ids, weights
+
+
+def moe_plan(ids: torch.Tensor, num_experts: int, workspace: torch.Tensor) -> None:
+    """Sort the (token, slot) pairs of `ids` (int32 [M, top_k]) by expert into `workspace` (uint8, moe_workspace_bytes)."""
+    _dev(ids, "ids")
+    assert ids.dim() == 2 and ids.is_contiguous() and ids.dtype == torch.int32 and workspace.dtype == torch.uint8
+    _check(lib().nvl_moe_plan(ids.data_ptr(), ids.shape[0], num_experts, ids.shape[1], workspace.data_ptr(),
+                              workspace.numel(), _stream()))
+
+
+def moe_experts(x: torch.Tensor, w_gate_up: torch.Tensor, w_down: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor,
+                workspace: torch.Tensor, out: torch.Tensor | None = None, packed: bool = False) -> torch.Tensor:
+    """out[t] = bf16(sum_j weights[t, j] * down_e(silu(gate_e(x[t])) * up_e(x[t]))), e = ids[t, j], for the plan that
+    `moe_plan(ids, ...)` left in `workspace`. w_gate_up [E, 2 * inter, H], w_down [E, H, inter] bf16 (`packed`: their
+    pack_weight_tiles() copies, made over the stacked [E * n, k] matrices)."""
+    _dev(x, "x")
+    assert x.dim() == 2 and x.is_contiguous() and w_gate_up.is_contiguous() and w_down.is_contiguous()
+    assert x.dtype == torch.bfloat16 and w_gate_up.dtype == torch.bfloat16 and w_down.dtype == torch.bfloat16
+    m, hidden = x.shape
+    e, hid2, inter = w_down.shape
+    assert hid2 == hidden and tuple(w_gate_up.shape) == (e, 2 * inter, hidden)
+    assert ids.dtype == torch.int32 and weights.dtype == torch.float32 and ids.is_contiguous() and weights.is_contiguous()
+    assert ids.shape[0] == m and ids.shape == weights.shape and workspace.dtype == torch.uint8
+    if out is None:
+        out = torch.empty_like(x)
+    _check(lib().nvl_moe_experts(x.data_ptr(), w_gate_up.data_ptr(), w_down.data_ptr(), ids.data_ptr(),
+                                 weights.data_ptr(), out.data_ptr(), m, hidden, inter, e, ids.shape[1],
+                                 1 if packed else 0, workspace.data_ptr(), workspace.numel(), _stream()))
+    return out
 
 
 def rope_neox(positions: torch.Tensor, cos_sin: torch.Tensor, x: torch.Tensor,

@@ -20,6 +20,8 @@ with the GEMMs on the hand-written skinny kernel (nvl_linear_decode).
 """
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import nn
 
@@ -27,7 +29,7 @@ from .api import model_geometry
 from .attn_meta import get_context
 from .layers import (Attention, MergedColumnParallelLinear, ParallelLMHead, QKVParallelLinear, RMSNorm,
                      RowParallelLinear, SiluAndMul, VocabParallelEmbedding, get_rope)
-from . import tp
+from . import ops, tp
 
 
 class Qwen3Attention(nn.Module):
@@ -75,13 +77,82 @@ class Qwen3MLP(nn.Module):
         return self.down_proj.forward_decode(self.gate_up_proj.forward_silu(x))
 
 
+class Qwen3MoeSparseBlock(nn.Module):
+    """The feed-forward block of the `qwen3_moe` models (Qwen3-30B-A3B, -235B-A22B): a router picks `top_k` of
+    `num_experts` SwiGLU experts per token. Three parameters — `gate` [E, hidden] (checkpoint `mlp.gate.weight`),
+    `experts_gate_up` [E, 2 * inter, hidden] and `experts_down` [E, hidden, inter] (the checkpoint's
+    `mlp.experts.{e}.{gate,up,down}_proj.weight`, stacked) — and three kernel calls: ops.moe_route -> moe_plan ->
+    moe_experts. bf16 rows in, bf16 rows out; the workspace is handed in by the runner (`set_workspace`) and shared by
+    all layers; more rows than it holds are served in consecutive chunks."""
+
+    def __init__(self, hidden_size: int, moe_intermediate_size: int, num_experts: int, top_k: int, norm_topk_prob: bool):
+        super().__init__()
+        self.num_experts, self.top_k, self.norm_topk_prob = num_experts, top_k, bool(norm_topk_prob)
+        self.hidden, self.inter = hidden_size, moe_intermediate_size
+        self.gate = nn.Parameter(torch.empty(num_experts, hidden_size), requires_grad=False)
+        self.experts_gate_up = nn.Parameter(torch.empty(num_experts, 2 * moe_intermediate_size, hidden_size),
+                                            requires_grad=False)
+        self.experts_down = nn.Parameter(torch.empty(num_experts, hidden_size, moe_intermediate_size), requires_grad=False)
+        self.experts_gate_up.weight_loader = self._load_gate_up
+        self.experts_down.weight_loader = self._load_down
+        self.gate_up_packed: torch.Tensor | None = None      # tile-packed copies (pack_for_decode): both or neither
+        self.down_packed: torch.Tensor | None = None
+        self.workspace: torch.Tensor | None = None
+        self.max_tokens = 0
+
+    def _load_gate_up(self, param: nn.Parameter, loaded: torch.Tensor, shard) -> None:
+        expert, half = shard                                  # half 0: gate_proj rows, 1: up_proj rows
+        param.data[expert, half * self.inter:(half + 1) * self.inter].copy_(loaded)
+
+    def _load_down(self, param: nn.Parameter, loaded: torch.Tensor, shard) -> None:
+        param.data[shard[0]].copy_(loaded)
+
+    def workspace_bytes(self, max_tokens: int) -> int:
+        return ops.moe_workspace_bytes(max_tokens, self.hidden, self.inter, self.num_experts, self.top_k)
+
+    def set_workspace(self, workspace: torch.Tensor, max_tokens: int) -> None:
+        assert workspace.dtype == torch.uint8 and workspace.numel() >= self.workspace_bytes(max_tokens)
+        self.workspace, self.max_tokens = workspace, max_tokens
+
+    def pack_for_decode(self, budget_bytes: float = float("inf")) -> int:
+        """Tile-packed copies of the stacked expert matrices (ops.pack_weight_tiles over [E * n, k]); returns the extra
+        bytes, or -1 when they do not fit `budget_bytes` (the kernels then stream the row-major parameters)."""
+        if os.environ.get("NVL_PACKED_WEIGHTS", "1") == "0":   # (A/B measurements, as LinearBase.pack_for_decode)
+            return 0
+        need = (self.experts_gate_up.numel() + self.experts_down.numel()) * 2
+        if need > budget_bytes:
+            return -1
+        gu, dn = self.experts_gate_up.data, self.experts_down.data
+        self.gate_up_packed = ops.pack_weight_tiles(gu.view(-1, gu.shape[-1])).view(gu.shape)
+        self.down_packed = ops.pack_weight_tiles(dn.view(-1, dn.shape[-1])).view(dn.shape)
+        return need
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.workspace is None:
+            raise ops.NvlError("Qwen3MoeSparseBlock has no workspace (set_workspace): the engine allocates it at load")
+        packed = self.gate_up_packed is not None
+        gu = self.gate_up_packed if packed else self.experts_gate_up
+        dn = self.down_packed if packed else self.experts_down
+        out = torch.empty_like(x)
+        for r0 in range(0, x.shape[0], self.max_tokens):
+            xs = x[r0:r0 + self.max_tokens]
+            ids, wts = ops.moe_route(xs, self.gate, self.top_k, self.norm_topk_prob)
+            ops.moe_plan(ids, self.num_experts, self.workspace)
+            ops.moe_experts(xs, gu, dn, ids, wts, self.workspace, out=out[r0:r0 + self.max_tokens], packed=packed)
+        return out
+
+
 class Qwen3DecoderLayer(nn.Module):
 
     def __init__(self, config, geo: dict):
         super().__init__()
         self.self_attn = Qwen3Attention(geo, config.num_attention_heads, config.num_key_value_heads,
                                         qkv_bias=getattr(config, "attention_bias", True))     # default as models/qwen3.py:133
-        self.mlp = Qwen3MLP(config.hidden_size, config.intermediate_size, config.hidden_act)
+        if geo.get("num_experts"):
+            self.mlp = Qwen3MoeSparseBlock(config.hidden_size, geo["moe_inter"], geo["num_experts"], geo["top_k"],
+                                           geo["norm_topk_prob"])
+        else:
+            self.mlp = Qwen3MLP(config.hidden_size, config.intermediate_size, config.hidden_act)
         self.input_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
@@ -141,3 +212,22 @@ class Qwen3ForCausalLM(nn.Module):
     def compute_logits_shard(self, hidden_states: torch.Tensor) -> torch.Tensor:
         """This rank's vocabulary slice of the logits (TP > 1: sampled shard-wise, never gathered)."""
         return self.lm_head.forward_shard(hidden_states)
+
+
+class Qwen3MoeForCausalLM(Qwen3ForCausalLM):
+    """`model_type: "qwen3_moe"`: the same decoder with Qwen3MoeSparseBlock as every layer's feed-forward block (the
+    geometry carries num_experts / top_k / moe_inter, Qwen3DecoderLayer picks the block from it)."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        assert self.geo["num_experts"], "Qwen3MoeForCausalLM needs a qwen3_moe config (num_experts)"
+
+    def allocate_moe_workspace(self, max_tokens: int) -> int:
+        """ONE workspace for the MoE blocks of every layer (they run one after the other), sized for `max_tokens` rows
+        per call; longer batches are chunked by the block. Returns its bytes."""
+        blocks = [m for m in self.modules() if isinstance(m, Qwen3MoeSparseBlock)]
+        nbytes = blocks[0].workspace_bytes(max_tokens)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=blocks[0].gate.device)
+        for b in blocks:
+            b.set_workspace(ws, max_tokens)
+        return nbytes

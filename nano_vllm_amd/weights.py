@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import json
 import os
+import re
 import zlib
 from glob import glob
 
@@ -46,8 +47,25 @@ QWEN3_SHAPES = {
     "qwen3-32b-tp4rank": (5120, 6400, 64, 16, 2, False),     # ... and of tensor_parallel_size = 4 (BASELINE config 4)
 }
 
+QWEN3_MOE_SHAPES = {
+    # name: hidden, moe_intermediate, layers, heads, kv_heads, tie, num_experts, experts per token, norm_topk_prob
+    "qwen3-30b-a3b": (2048, 768, 48, 32, 4, False, 128, 8, True),
+    "qwen3-30b-a3b-2l": (2048, 768, 2, 32, 4, False, 128, 8, True),      # two full-width layers (tests, tools/moe_bench.py)
+    "qwen3-moe-tiny": (256, 128, 2, 4, 2, True, 8, 2, True),             # qwen3-tiny's attention, 8 experts of width 128
+}
+
 
 def qwen3_config_dict(name: str, vocab_size: int = 151936, max_position_embeddings: int = 40960) -> dict:
+    if name.lower() in QWEN3_MOE_SHAPES:
+        hidden, moe_inter, layers, heads, kv, tie, experts, top_k, norm = QWEN3_MOE_SHAPES[name.lower()]
+        cfg = qwen3_config_dict("qwen3-tiny", vocab_size, max_position_embeddings)
+        cfg.update({
+            "architectures": ["Qwen3MoeForCausalLM"], "model_type": "qwen3_moe", "hidden_size": hidden,
+            "intermediate_size": 8 * moe_inter, "moe_intermediate_size": moe_inter, "num_hidden_layers": layers,
+            "num_attention_heads": heads, "num_key_value_heads": kv, "tie_word_embeddings": tie, "num_experts": experts,
+            "num_experts_per_tok": top_k, "norm_topk_prob": norm, "decoder_sparse_step": 1, "mlp_only_layers": [],
+        })
+        return cfg
     hidden, inter, layers, heads, kv, tie = QWEN3_SHAPES[name.lower()]
     return {
         "architectures": ["Qwen3ForCausalLM"], "model_type": "qwen3", "hidden_size": hidden,
@@ -60,8 +78,9 @@ def qwen3_config_dict(name: str, vocab_size: int = 151936, max_position_embeddin
 
 
 def parameter_shapes(cfg: dict) -> dict[str, tuple]:
-    """HF checkpoint tensor names -> shapes for a Qwen3 config dict."""
+    """HF checkpoint tensor names -> shapes for a Qwen3 / Qwen3-MoE config dict."""
     h, inter, d = cfg["hidden_size"], cfg["intermediate_size"], cfg["head_dim"]
+    experts, moe_inter = cfg.get("num_experts", 0), cfg.get("moe_intermediate_size", 0)
     nh, nkv, v = cfg["num_attention_heads"], cfg["num_key_value_heads"], cfg["vocab_size"]
     out = {"model.embed_tokens.weight": (v, h), "model.norm.weight": (h,)}
     if not cfg["tie_word_embeddings"]:
@@ -73,9 +92,16 @@ def parameter_shapes(cfg: dict) -> dict[str, tuple]:
             p + "self_attn.q_proj.weight": (nh * d, h), p + "self_attn.k_proj.weight": (nkv * d, h),
             p + "self_attn.v_proj.weight": (nkv * d, h), p + "self_attn.o_proj.weight": (h, nh * d),
             p + "self_attn.q_norm.weight": (d,), p + "self_attn.k_norm.weight": (d,),
-            p + "mlp.gate_proj.weight": (inter, h), p + "mlp.up_proj.weight": (inter, h),
-            p + "mlp.down_proj.weight": (h, inter),
         })
+        if experts:
+            out[p + "mlp.gate.weight"] = (experts, h)
+            for e in range(experts):
+                q = f"{p}mlp.experts.{e}."
+                out.update({q + "gate_proj.weight": (moe_inter, h), q + "up_proj.weight": (moe_inter, h),
+                            q + "down_proj.weight": (h, moe_inter)})
+        else:
+            out.update({p + "mlp.gate_proj.weight": (inter, h), p + "mlp.up_proj.weight": (inter, h),
+                        p + "mlp.down_proj.weight": (h, inter)})
     return out
 
 
@@ -126,8 +152,20 @@ def write_synthetic_checkpoint(path: str, name: str = "qwen3-0.6b", seed: int = 
 
 
 # ------------------------------------------------------------------------------------------------
+_EXPERT_NAME = re.compile(r"^(.*\.mlp)\.experts\.(\d+)\.(gate_proj|up_proj|down_proj)\.weight$")
+
+
 def _route(model: nn.Module, weight_name: str):
-    """checkpoint tensor name -> (parameter, shard_id | None)."""
+    """checkpoint tensor name -> (parameter, shard_id | None). Qwen3-MoE: `mlp.experts.{e}.{gate,up,down}_proj.weight` are
+    slices (expert, half) of the block's stacked `experts_gate_up` / `experts_down`; `mlp.gate.weight` is its router."""
+    m = _EXPERT_NAME.match(weight_name)
+    if m:
+        block, expert, proj = m.group(1), int(m.group(2)), m.group(3)
+        if proj == "down_proj":
+            return model.get_parameter(block + ".experts_down"), (expert, 0)
+        return model.get_parameter(block + ".experts_gate_up"), (expert, 0 if proj == "gate_proj" else 1)
+    if weight_name.endswith(".mlp.gate.weight"):
+        return model.get_parameter(weight_name[:-len(".weight")]), None
     for frag, (fused, shard) in getattr(model, "packed_modules_mapping", {}).items():
         if frag in weight_name:
             return model.get_parameter(weight_name.replace(frag, fused)), shard
@@ -172,6 +210,8 @@ def init_dummy_weights(model: nn.Module, hf_config, seed: int = 0) -> None:
         "vocab_size": hf_config.vocab_size, "num_hidden_layers": hf_config.num_hidden_layers,
         "tie_word_embeddings": bool(getattr(hf_config, "tie_word_embeddings", False)),
     }
+    if getattr(hf_config, "model_type", "qwen3") == "qwen3_moe":
+        cfg.update(num_experts=hf_config.num_experts, moe_intermediate_size=hf_config.moe_intermediate_size)
     device = next(model.parameters()).device
     for name, shape in parameter_shapes(cfg).items():
         param, shard = _route(model, name)
