@@ -198,6 +198,26 @@ int nvl_moe_experts(const void* x, const void* w_gate_up, const void* w_down, co
                     const float* topk_w, void* out, int64_t m, int hidden, int inter, int E, int top_k,
                     int weight_layout, void* workspace, size_t workspace_bytes, void* stream);
 
+/* MXFP4 expert weights (opt-in: LLM(..., weight_dtype="mxfp4"); csrc/moe_mxfp4.hip). OCP microscaling: element e2m1
+ * (codes 0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6; bit 3 = sign), one e8m0 scale byte s (= 2^(s - 127)) per row and 32
+ * consecutive k. Quantisation of a block with A = max |w|: A = 0 -> byte 127, codes 0; else E = floor(log2 A) - 2
+ * (clamped to >= -126: scale byte 0 never occurs), byte E + 127, each element w / 2^E rounded to the nearest code
+ * magnitude, ties to the even code, magnitudes above 6 to 6. Weights are finite. Idempotent on its own output.
+ *   codes:  uint8 [n/16][k/128][64 lanes][16 bytes], lane = 16 lq + l15; byte 4 kb + b of a lane = row 16 tile + l15,
+ *           k = 128 step + 32 kb + 8 lq + 2 b in the low nibble, that k + 1 in the high nibble (the lane's
+ *           v_mfma_f32_16x16x32_bf16 A fragments of the step's four k blocks).
+ *   scales: uint8 [n][k/32], row-major.
+ *   nvl_quant_pack_mxfp4: one pass over a row-major bf16 [n, k] matrix (n % 16 == 0, k % 128 == 0, 16-byte-aligned
+ *     pointers) writes both.
+ *   nvl_moe_experts_mxfp4: nvl_moe_experts (same plan, workspace, three launches, rounding points, fixed summation
+ *     order) over the quantised stacked matrices [E * 2 * inter, hidden] and [E * hidden, inter]: the weights enter
+ *     the matrix instruction as bf16(code * scale), exactly. */
+int nvl_quant_pack_mxfp4(const void* w_bf16, int64_t n, int64_t k, void* codes_out, void* scales_out, void* stream);
+int nvl_moe_experts_mxfp4(const void* x, const void* gu_codes, const void* gu_scales, const void* dn_codes,
+                          const void* dn_scales, const int32_t* topk_ids, const float* topk_w, void* out, int64_t m,
+                          int hidden, int inter, int E, int top_k, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* ---- Rotary embedding -----------------------------------------------------
  * Replaces RotaryEmbedding.forward / apply_rotary_emb
  * (layers/rotary_embedding.py:6-14, 37-48): neox (half-split) rotation from a

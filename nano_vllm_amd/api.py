@@ -17,6 +17,10 @@ Extensions (all optional, behaviour-neutral when unset):
     with a power-of-two scale per 128 x 128 block and streams them through nvl_linear_wide_fp8 (half the weight bytes
     per decode step, a half-size packed copy). The bf16 parameter is overwritten with the dequantised values, so
     prefill and decode compute with the same matrix. Outside the reference's numerics: opt-in, default "bf16".
+  * Config.weight_dtype = "mxfp4" (qwen3_moe models only) quantises the expert matrices at load time to OCP MXFP4 —
+    e2m1 elements, one power-of-two scale byte per row and 32 k — and frees their bf16 storage: prefill and decode
+    both run nvl_moe_experts_mxfp4 (about 3.76 x fewer expert bytes, resident and streamed). Attention, router,
+    embedding and lm_head stay bf16. A dense model is refused; "fp8" stays refused for qwen3_moe.
 """
 from __future__ import annotations
 
@@ -57,6 +61,7 @@ class Config:
     dummy_weights: bool = False
     kv_cache_dtype: str = "bf16"         # "fp8": OCP e4m3 KV cache (halves decode bytes; outside the reference's numerics)
     weight_dtype: str = "bf16"           # "fp8": block-scaled e4m3 decode projections (halves weight bytes; same caveat)
+    #                                      "mxfp4": 4-bit expert matrices of a qwen3_moe model (module docstring)
 
     def __post_init__(self):
         assert os.path.isdir(self.model), f"model directory not found: {self.model}"
@@ -68,18 +73,20 @@ class Config:
         self.max_model_len = min(self.max_model_len, self.hf_config.max_position_embeddings)
         assert self.max_num_batched_tokens >= 1 and self.max_num_seqs >= 1
         assert self.kv_cache_dtype in ("bf16", "fp8"), "kv_cache_dtype must be 'bf16' or 'fp8'"
-        assert self.weight_dtype in ("bf16", "fp8"), "weight_dtype must be 'bf16' or 'fp8'"
+        assert self.weight_dtype in ("bf16", "fp8", "mxfp4"), "weight_dtype must be 'bf16', 'fp8' or 'mxfp4'"
+        if self.weight_dtype == "mxfp4" and getattr(self.hf_config, "model_type", "qwen3") != "qwen3_moe":
+            raise ValueError("weight_dtype='mxfp4' covers the expert weights of a qwen3_moe model only (dense models: 'fp8')")
         check_moe_scope(self.hf_config, self.tensor_parallel_size, self.weight_dtype)
 
 
 def check_moe_scope(hf_config, tp: int = 1, weight_dtype: str = "bf16") -> None:
-    """A `qwen3_moe` config is served on one GPU with bf16 experts, every layer sparse, no shared expert; anything else
-    is refused here, at load, rather than computed wrongly."""
+    """A `qwen3_moe` config is served on one GPU with bf16 or MXFP4 experts, every layer sparse, no shared expert;
+    anything else is refused here, at load, rather than computed wrongly."""
     if getattr(hf_config, "model_type", "qwen3") != "qwen3_moe":
         return
     if tp != 1:
         raise ValueError("qwen3_moe: tensor_parallel_size > 1 is not supported (the expert kernels are single-GPU)")
-    if weight_dtype != "bf16":
+    if weight_dtype not in ("bf16", "mxfp4"):
         raise ValueError("qwen3_moe: weight_dtype='fp8' is not supported (expert weights stay bf16)")
     if getattr(hf_config, "decoder_sparse_step", 1) != 1 or list(getattr(hf_config, "mlp_only_layers", None) or []):
         raise ValueError("qwen3_moe: decoder_sparse_step != 1 / mlp_only_layers are not supported (every layer is sparse)")

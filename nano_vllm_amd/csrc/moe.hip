@@ -29,40 +29,11 @@
 //   Surplus workgroups (padded row blocks) leave as a whole before the first barrier.
 // Rounding points are nvl_linear_decode's: gate and up are rounded to bf16 before the activation, h is bf16, the down
 // projection stays fp32 until the combine rounds once.
-#include "common.h"
+// (nvl_moe_experts_mxfp4, the same three launches over 4-bit expert weights, is moe_mxfp4.hip; moe_common.h holds what
+// the two share.)
+#include "moe_common.h"
 
 namespace {
-
-constexpr int kRowBlock = 128;           // rows per row block (8 MFMA row tiles)
-constexpr int kMaxE = 256;
-constexpr int kMaxTopK = 8;
-
-struct MoeLayout {
-  size_t offsets, sorted, pos, blocks, h, y, index_end, total;
-  int64_t pairs;
-  int64_t nb_max;
-};
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Workspace of a call with m tokens: the index section depends on (m, E, top_k) only (nvl_moe_plan knows nothing else).
-MoeLayout moe_layout(int64_t m, int hidden, int inter, int E, int top_k) {
-  MoeLayout l;
-  l.pairs = m * top_k;
-  l.nb_max = l.pairs / kRowBlock + (l.pairs < E ? l.pairs : E);
-  size_t o = 0;
-  l.offsets = o; o = align256(o + (size_t)(E + 1) * 4);
-  l.sorted = o;  o = align256(o + (size_t)l.pairs * 4);
-  l.pos = o;     o = align256(o + (size_t)l.pairs * 4);
-  l.blocks = o;  o = align256(o + (size_t)l.nb_max * 16);
-  l.index_end = o;
-  l.h = o;       o = align256(o + (size_t)l.pairs * inter * 2);
-  l.y = o;       o = align256(o + (size_t)l.pairs * hidden * 4);
-  l.total = o;
-  return l;
-}
-
-__device__ __forceinline__ float silu_f32(float g) { return g / (1.f + __expf(-g)); }
 
 // ---- router -------------------------------------------------------------------------------------------------------
 // One wave (= one workgroup) per token. HC = 16-byte chunks of the x row per lane (hidden <= HC * 512), held as fp32.
@@ -395,16 +366,13 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const float* __restric
   }
 }
 
-bool moe_shape_ok(int64_t m, int E, int top_k, const char* who) {
-  if (!(m >= 0 && m <= (1 << 20) && E >= 1 && E <= kMaxE && top_k >= 1 && top_k <= kMaxTopK && top_k <= E)) {
-    nvl_set_error("%s: m=%lld E=%d top_k=%d: need 0 <= m <= 2^20, 1 <= E <= 256, 1 <= top_k <= 8, top_k <= E", who,
-                  (long long)m, E, top_k);
-    return false;
-  }
-  return true;
-}
-
 }  // namespace
+
+void moe_launch_combine(const float* y, const int* pos, const float* topk_w, void* out, int64_t m, int hidden, int top_k,
+                        int pairs, hipStream_t stream) {
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)m), dim3(256), 0, stream, y, pos, topk_w, (bf16_t*)out, hidden,
+                     top_k, pairs);
+}
 
 extern "C" size_t nvl_moe_workspace_bytes(int64_t max_tokens, int hidden, int inter, int E, int top_k) {
   if (max_tokens < 1 || max_tokens > (1 << 20) || hidden < 128 || hidden % 128 || inter < 128 || inter % 128 || E < 1 ||
@@ -484,7 +452,6 @@ extern "C" int nvl_moe_experts(const void* x, const void* w_gate_up, const void*
     hipLaunchKernelGGL((moe_gemm_kernel<EPI_F32, false>), g2, dim3(256), 0, st, (const bf16_t*)h, (const bf16_t*)w_down,
                        (void*)y, blocks, sorted, top_k, inter, hidden);
   }
-  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)m), dim3(256), 0, st, (const float*)y,
-                     (const int*)(ws + l.pos), topk_w, (bf16_t*)out, hidden, top_k, (int)l.pairs);
+  moe_launch_combine(y, (const int*)(ws + l.pos), topk_w, out, m, hidden, top_k, (int)l.pairs, st);
   return nvl_check_launch("nvl_moe_experts");
 }

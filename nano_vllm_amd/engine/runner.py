@@ -356,13 +356,17 @@ class ModelRunner:
         min(NVL_PACKED_BUDGET_FRAC (default 0.25) x device memory, half of what is free once the weights are loaded);
         projections are packed in model order until the next one no longer fits, the rest keep the row-major weight
         stream (slower decode GEMM, same results bit for bit) — on a 192 GB part Qwen3-32B packs its first ~48 GB and
-        keeps its KV pool. Returns (bytes packed, projections left unpacked for lack of budget)."""
+        keeps its KV pool. weight_dtype="mxfp4" replaces the MoE blocks' expert matrices by their 4-bit form instead.
+        Returns (bytes packed or quantised, projections left unpacked for lack of budget)."""
         from ..layers import LinearBase, ParallelLMHead
         free, total = torch.cuda.mem_get_info(self.device)
         budget = min(float(os.environ.get("NVL_PACKED_BUDGET_FRAC", "0.25")) * total, 0.5 * free)
-        used = skipped = 0
+        used = skipped = quantised = 0
         for m in self.model.modules():
             if isinstance(m, Qwen3MoeSparseBlock):       # the stacked expert matrices, under the same budget
+                if self.config.weight_dtype == "mxfp4":  # ... or quantised IN PLACE of the bf16 parameters: that frees
+                    quantised += m.pack_for_decode(weight_dtype="mxfp4")     # memory, so it is reported, not budgeted
+                    continue
                 got = m.pack_for_decode(budget - used)
                 if got < 0:
                     skipped += 1
@@ -377,7 +381,7 @@ class ModelRunner:
                     skipped += 1
                 else:
                     used += got
-        return used, skipped
+        return used + quantised, skipped
 
     # ------------------------------------------------------------------ lifecycle / TP control channel
     def exit(self):

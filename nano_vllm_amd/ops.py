@@ -43,6 +43,9 @@ SIGNATURES = {
     "nvl_moe_plan": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "nvl_moe_experts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                 c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "nvl_quant_pack_mxfp4": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nvl_moe_experts_mxfp4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int64, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "nvl_rope_neox": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "nvl_store_kvcache": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64,
                                   c_int, c_void_p]),
@@ -401,6 +404,44 @@ def moe_experts(x: torch.Tensor, w_gate_up: torch.Tensor, w_down: torch.Tensor, 
     _check(lib().nvl_moe_experts(x.data_ptr(), w_gate_up.data_ptr(), w_down.data_ptr(), ids.data_ptr(),
                                  weights.data_ptr(), out.data_ptr(), m, hidden, inter, e, ids.shape[1],
                                  1 if packed else 0, workspace.data_ptr(), workspace.numel(), _stream()))
+    return out
+
+
+def quant_pack_mxfp4(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Row-major bf16 [N, K] -> (codes uint8 [N/16, K/128, 64, 16], scales uint8 [N, K/32]): OCP MXFP4 (e2m1 elements,
+    one e8m0 scale per row and 32 k), codes in the A-fragment tile order of nvl_moe_experts_mxfp4 (include/nvl.h)."""
+    _dev(w, "w")
+    assert w.dim() == 2 and w.is_contiguous() and w.dtype == torch.bfloat16
+    n, k = w.shape
+    if n % 16 or k % 128:
+        raise NvlError(f"nvl_quant_pack_mxfp4: n={n} must be a multiple of 16 and k={k} a multiple of 128")
+    codes = torch.empty((n // 16, k // 128, 64, 16), dtype=torch.uint8, device=w.device)
+    scales = torch.empty((n, k // 32), dtype=torch.uint8, device=w.device)
+    _check(lib().nvl_quant_pack_mxfp4(w.data_ptr(), n, k, codes.data_ptr(), scales.data_ptr(), _stream()))
+    return codes, scales
+
+
+def moe_experts_mxfp4(x: torch.Tensor, gu: torch.Tensor, gu_scales: torch.Tensor, dn: torch.Tensor, dn_scales: torch.Tensor,
+                      ids: torch.Tensor, weights: torch.Tensor, workspace: torch.Tensor,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """moe_experts over MXFP4 experts: (`gu`, `gu_scales`) = quant_pack_mxfp4 of the stacked gate|up [E * 2 * inter, H],
+    (`dn`, `dn_scales`) of the stacked down [E * H, inter]. E and inter follow from the scale shapes."""
+    _dev(x, "x")
+    assert x.dim() == 2 and x.is_contiguous() and x.dtype == torch.bfloat16
+    for t in (gu, gu_scales, dn, dn_scales):
+        assert t.is_contiguous() and t.dtype == torch.uint8
+    m, hidden = x.shape
+    inter = dn_scales.shape[1] * 32
+    e = dn_scales.shape[0] // hidden
+    assert tuple(dn_scales.shape) == (e * hidden, inter // 32) and tuple(gu_scales.shape) == (e * 2 * inter, hidden // 32)
+    assert gu.numel() == e * inter * hidden and dn.numel() * 2 == e * inter * hidden
+    assert ids.dtype == torch.int32 and weights.dtype == torch.float32 and ids.is_contiguous() and weights.is_contiguous()
+    assert ids.shape[0] == m and ids.shape == weights.shape and workspace.dtype == torch.uint8
+    if out is None:
+        out = torch.empty_like(x)
+    _check(lib().nvl_moe_experts_mxfp4(x.data_ptr(), gu.data_ptr(), gu_scales.data_ptr(), dn.data_ptr(), dn_scales.data_ptr(),
+                                       ids.data_ptr(), weights.data_ptr(), out.data_ptr(), m, hidden, inter, e, ids.shape[1],
+                                       workspace.data_ptr(), workspace.numel(), _stream()))
     return out
 
 

@@ -83,7 +83,8 @@ class Qwen3MoeSparseBlock(nn.Module):
     `experts_gate_up` [E, 2 * inter, hidden] and `experts_down` [E, hidden, inter] (the checkpoint's
     `mlp.experts.{e}.{gate,up,down}_proj.weight`, stacked) — and three kernel calls: ops.moe_route -> moe_plan ->
     moe_experts. bf16 rows in, bf16 rows out; the workspace is handed in by the runner (`set_workspace`) and shared by
-    all layers; more rows than it holds are served in consecutive chunks."""
+    all layers; more rows than it holds are served in consecutive chunks. After pack_for_decode(weight_dtype="mxfp4") the
+    expert matrices exist as MXFP4 codes + scales only and the last call is ops.moe_experts_mxfp4."""
 
     def __init__(self, hidden_size: int, moe_intermediate_size: int, num_experts: int, top_k: int, norm_topk_prob: bool):
         super().__init__()
@@ -97,6 +98,8 @@ class Qwen3MoeSparseBlock(nn.Module):
         self.experts_down.weight_loader = self._load_down
         self.gate_up_packed: torch.Tensor | None = None      # tile-packed copies (pack_for_decode): both or neither
         self.down_packed: torch.Tensor | None = None
+        # (gate|up codes, scales, down codes, scales) once pack_for_decode(weight_dtype="mxfp4") has run
+        self.mxfp4: tuple[torch.Tensor, ...] | None = None
         self.workspace: torch.Tensor | None = None
         self.max_tokens = 0
 
@@ -114,9 +117,21 @@ class Qwen3MoeSparseBlock(nn.Module):
         assert workspace.dtype == torch.uint8 and workspace.numel() >= self.workspace_bytes(max_tokens)
         self.workspace, self.max_tokens = workspace, max_tokens
 
-    def pack_for_decode(self, budget_bytes: float = float("inf")) -> int:
+    def pack_for_decode(self, budget_bytes: float = float("inf"), weight_dtype: str = "bf16") -> int:
         """Tile-packed copies of the stacked expert matrices (ops.pack_weight_tiles over [E * n, k]); returns the extra
-        bytes, or -1 when they do not fit `budget_bytes` (the kernels then stream the row-major parameters)."""
+        bytes, or -1 when they do not fit `budget_bytes` (the kernels then stream the row-major parameters).
+        weight_dtype="mxfp4": the stacked matrices are quantised to MXFP4 (ops.quant_pack_mxfp4: 4-bit codes + one scale
+        byte per 32 k) and the bf16 parameters' storage is RELEASED — prefill and decode both run nvl_moe_experts_mxfp4,
+        nothing needs the bf16 matrix again. The call frees more than it takes, so the budget does not apply; returns
+        the bytes of codes and scales."""
+        if weight_dtype == "mxfp4":
+            if self.mxfp4 is None:
+                packed = []
+                for p in (self.experts_gate_up, self.experts_down):
+                    packed += ops.quant_pack_mxfp4(p.data.view(-1, p.shape[-1]))
+                    p.data = torch.empty(0, dtype=p.dtype, device=p.device)
+                self.mxfp4 = tuple(packed)
+            return sum(t.numel() for t in self.mxfp4)
         if os.environ.get("NVL_PACKED_WEIGHTS", "1") == "0":   # (A/B measurements, as LinearBase.pack_for_decode)
             return 0
         need = (self.experts_gate_up.numel() + self.experts_down.numel()) * 2
@@ -138,7 +153,10 @@ class Qwen3MoeSparseBlock(nn.Module):
             xs = x[r0:r0 + self.max_tokens]
             ids, wts = ops.moe_route(xs, self.gate, self.top_k, self.norm_topk_prob)
             ops.moe_plan(ids, self.num_experts, self.workspace)
-            ops.moe_experts(xs, gu, dn, ids, wts, self.workspace, out=out[r0:r0 + self.max_tokens], packed=packed)
+            if self.mxfp4 is not None:
+                ops.moe_experts_mxfp4(xs, *self.mxfp4, ids, wts, self.workspace, out=out[r0:r0 + self.max_tokens])
+            else:
+                ops.moe_experts(xs, gu, dn, ids, wts, self.workspace, out=out[r0:r0 + self.max_tokens], packed=packed)
         return out
 
 

@@ -5,6 +5,10 @@ decode step does), the loop eagerly (its row counts are host data: it cannot be 
 Writes a JSON table: us of each side, unique expert bytes touched, achieved GB/s of the block against the 8 TB/s peak.
 
     python tools/moe_bench.py [--out profiles/moe_block_30b_a3b.json]
+
+--weight-dtype mxfp4 instead times nvl_moe_experts_mxfp4 against nvl_moe_experts on the same routing (main_mxfp4):
+
+    python tools/moe_bench.py --weight-dtype mxfp4 [--out profiles/moe_block_30b_a3b_mxfp4.json]
 """
 import argparse
 import json
@@ -79,7 +83,62 @@ def main(out_path):
         json.dump(dict(shape=dict(hidden=HIDDEN, inter=INTER, experts=E, top_k=K), rows=rows), fh, indent=1)
 
 
+def main_mxfp4(out_path):
+    """nvl_moe_experts_mxfp4 against nvl_moe_experts (tile-packed bf16) on the same routing, in the same process, the
+    same protocol. The bf16 side runs on the DEQUANTISED matrices, so both compute the same numbers (max_diff reported);
+    bytes are the unique expert bytes each side streams (codes + scale bytes against bf16)."""
+    dev = torch.device("cuda")
+    rw = torch.randn(E, HIDDEN, device=dev).to(torch.bfloat16)
+    gu = (torch.randn(E * 2 * INTER, HIDDEN, device=dev) * HIDDEN ** -0.5).to(torch.bfloat16)
+    dn = (torch.randn(E * HIDDEN, INTER, device=dev) * INTER ** -0.5).to(torch.bfloat16)
+    q = ops.quant_pack_mxfp4(gu) + ops.quant_pack_mxfp4(dn)
+
+    def dequant(codes, scales, n, k):          # the code tiles back to a row-major bf16 matrix (include/nvl.h's index map)
+        mag = torch.tensor([0, .5, 1, 1.5, 2, 3, 4, 6, 0, -.5, -1, -1.5, -2, -3, -4, -6], device=dev)
+        c = codes.view(n // 16, k // 128, 4, 16, 4, 4).permute(0, 3, 1, 4, 2, 5).reshape(n, k // 2).long()
+        v = mag[torch.stack((c & 15, c >> 4), -1).view(n, k // 32, 32)]
+        return (v * torch.exp2(scales.float() - 127)[..., None]).view(n, k).to(torch.bfloat16)
+
+    gup = ops.pack_weight_tiles(dequant(q[0], q[1], *gu.shape)).view(E, 2 * INTER, HIDDEN)
+    dnp = ops.pack_weight_tiles(dequant(q[2], q[3], *dn.shape)).view(E, HIDDEN, INTER)
+    del gu, dn
+    ws = torch.empty(ops.moe_workspace_bytes(max(ROWS), HIDDEN, INTER, E, K), dtype=torch.uint8, device=dev)
+    rows = []
+    for m in ROWS:
+        x = torch.randn(m, HIDDEN, device=dev).to(torch.bfloat16)
+        ids, wts = ops.moe_route(x, rw, K, True)
+        ops.moe_plan(ids, E, ws)
+        out4, out16 = torch.empty_like(x), torch.empty_like(x)
+        sides = (lambda: ops.moe_experts_mxfp4(x, *q, ids, wts, ws, out=out4),
+                 lambda: ops.moe_experts(x, gup, dnp, ids, wts, ws, out=out16, packed=True))
+        graphs = []
+        for fn in sides:
+            fn()
+            torch.cuda.synchronize()
+            graphs.append(torch.cuda.CUDAGraph())
+            with torch.cuda.graph(graphs[-1]):
+                fn()
+        t4, t16 = (layers._time_cold(g.replay, dev, 5) * 1e3 for g in graphs)
+        err = ((out4.float() - out16.float()).abs().max() / out16.float().pow(2).mean().sqrt()).item()
+        touched = int(ids.unique().numel())
+        b16 = touched * 3 * INTER * HIDDEN * 2
+        b4 = b16 * 17 // 64                                       # 4 bits + one scale byte per 32 elements
+        rows.append(dict(m=m, experts_touched=touched, mxfp4_us=round(t4, 1), bf16_us=round(t16, 1),
+                         mxfp4_mbytes=round(b4 / 1e6, 1), bf16_mbytes=round(b16 / 1e6, 1),
+                         mxfp4_gbs=round(b4 / t4 / 1e3, 1), bf16_gbs=round(b16 / t16 / 1e3, 1),
+                         speedup=round(t16 / t4, 2), max_diff_over_rms_vs_bf16=round(err, 5)))
+        print(json.dumps(rows[-1]), flush=True)
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(dict(shape=dict(hidden=HIDDEN, inter=INTER, experts=E, top_k=K), rows=rows), fh, indent=1)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/moe_block_30b_a3b.json")
-    main(ap.parse_args().out)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--weight-dtype", choices=("bf16", "mxfp4"), default="bf16")
+    args = ap.parse_args()
+    if args.weight_dtype == "mxfp4":
+        main_mxfp4(args.out or "profiles/moe_block_30b_a3b_mxfp4.json")
+    else:
+        main(args.out or "profiles/moe_block_30b_a3b.json")
