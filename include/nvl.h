@@ -154,6 +154,21 @@ int nvl_linear_wide_fp8(const void* x, const void* w8_packed, const void* scales
                         int n, int k, int mode, void* workspace, size_t workspace_bytes, void* stream);
 int nvl_pack_weight_tiles_fp8(const void* w8, void* packed, int64_t n, int64_t k, void* stream);
 
+/* W8A16 TILE linear for ANY row count (opt-in: LLM(..., weight_dtype="fp8_only"); csrc/gemm_tile_fp8.hip): the same
+ * product on the same operands — `w8_packed` is what nvl_pack_weight_tiles_fp8 writes, `scales` fp32 [n/16][k/128] —
+ * for the rows nvl_linear_wide_fp8's plan refuses (every m > 256: prefill, decode batches of 257-512 sequences), so
+ * that the bf16 parameter the library GEMM needed can be released. m >= 1 (partial row tiles are masked; rows past m
+ * of `out` are not written), n % 16 == 0 (mode 1: n % 32 == 0), k % 128 == 0. No workspace, enqueue-only.
+ *   mode 0: bf16 [m, n].  mode 1: bf16 [m, n/2] = silu(bf16(gate)) * bf16(up), gate rows first, then up rows
+ *   (nvl_linear_wide mode 1's rounding point).  mode 2: NVL_EUNSUPPORTED (callers that want slabs take mode 0).
+ * SCALE CONTRACT (narrower than nvl_linear_wide_fp8's): every scale is a POWER OF TWO with e4m3 x scale a normal bf16
+ * — what the engine's quantiser produces. The kernel forms bf16(w8 x s) on the way to the matrix instruction, which
+ * is then exact: out = x . W_deq^T with fp32 accumulation, the matrix weight_dtype="fp8" multiplies in prefill, up to
+ * the summation order. Other scales are rounded to bf16 per weight (no per-block second accumulator is carried).
+ * The first call on a device opts one kernel into 96 KiB of LDS (hipFuncSetAttribute): make it before any capture. */
+int nvl_linear_tile_fp8(const void* x, const void* w8_packed, const void* scales, void* out, int64_t m,
+                        int n, int k, int mode, void* stream);
+
 /* Fused split-K reduction + residual add + RMSNorm: replaces
  * RMSNorm.add_rms_forward (layers/layernorm.py:28-40) when its input is the
  * fp32 partials of nvl_linear_decode mode 2:

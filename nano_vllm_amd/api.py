@@ -17,6 +17,11 @@ Extensions (all optional, behaviour-neutral when unset):
     with a power-of-two scale per 128 x 128 block and streams them through nvl_linear_wide_fp8 (half the weight bytes
     per decode step, a half-size packed copy). The bf16 parameter is overwritten with the dequantised values, so
     prefill and decode compute with the same matrix. Outside the reference's numerics: opt-in, default "bf16".
+  * Config.weight_dtype = "fp8_only" (dense models, one GPU) quantises exactly as "fp8" and then FREES the bf16
+    projections: rows above 256 (prefill, decode batches of 257-512 sequences) run nvl_linear_tile_fp8 on the same packed
+    e4m3 tiles instead of the library GEMM on a bf16 copy, so the projections occupy half of bf16's bytes and the KV pool
+    gets the rest. Same matrix as "fp8", another summation order in prefill. Refused for qwen3_moe and for
+    tensor_parallel_size > 1.
   * Config.weight_dtype = "mxfp4" (qwen3_moe models only) quantises the expert matrices at load time to OCP MXFP4 —
     e2m1 elements, one power-of-two scale byte per row and 32 k — and frees their bf16 storage: prefill and decode
     both run nvl_moe_experts_mxfp4 (about 3.76 x fewer expert bytes, resident and streamed). Attention, router,
@@ -61,6 +66,7 @@ class Config:
     dummy_weights: bool = False
     kv_cache_dtype: str = "bf16"         # "fp8": OCP e4m3 KV cache (halves decode bytes; outside the reference's numerics)
     weight_dtype: str = "bf16"           # "fp8": block-scaled e4m3 decode projections (halves weight bytes; same caveat)
+    #                                      "fp8_only": the same, and the bf16 projections are freed (module docstring)
     #                                      "mxfp4": 4-bit expert matrices of a qwen3_moe model (module docstring)
 
     def __post_init__(self):
@@ -73,7 +79,10 @@ class Config:
         self.max_model_len = min(self.max_model_len, self.hf_config.max_position_embeddings)
         assert self.max_num_batched_tokens >= 1 and self.max_num_seqs >= 1
         assert self.kv_cache_dtype in ("bf16", "fp8"), "kv_cache_dtype must be 'bf16' or 'fp8'"
-        assert self.weight_dtype in ("bf16", "fp8", "mxfp4"), "weight_dtype must be 'bf16', 'fp8' or 'mxfp4'"
+        assert self.weight_dtype in ("bf16", "fp8", "fp8_only", "mxfp4"), \
+            "weight_dtype must be 'bf16', 'fp8', 'fp8_only' or 'mxfp4'"
+        if self.weight_dtype == "fp8_only" and self.tensor_parallel_size > 1:
+            raise ValueError("weight_dtype='fp8_only' is single-GPU (the tensor-parallel GEMMs read the bf16 parameter): use 'fp8'")
         if self.weight_dtype == "mxfp4" and getattr(self.hf_config, "model_type", "qwen3") != "qwen3_moe":
             raise ValueError("weight_dtype='mxfp4' covers the expert weights of a qwen3_moe model only (dense models: 'fp8')")
         check_moe_scope(self.hf_config, self.tensor_parallel_size, self.weight_dtype)
@@ -87,7 +96,7 @@ def check_moe_scope(hf_config, tp: int = 1, weight_dtype: str = "bf16") -> None:
     if tp != 1:
         raise ValueError("qwen3_moe: tensor_parallel_size > 1 is not supported (the expert kernels are single-GPU)")
     if weight_dtype not in ("bf16", "mxfp4"):
-        raise ValueError("qwen3_moe: weight_dtype='fp8' is not supported (expert weights stay bf16)")
+        raise ValueError(f"qwen3_moe: weight_dtype='{weight_dtype}' is not supported (expert weights stay bf16)")
     if getattr(hf_config, "decoder_sparse_step", 1) != 1 or list(getattr(hf_config, "mlp_only_layers", None) or []):
         raise ValueError("qwen3_moe: decoder_sparse_step != 1 / mlp_only_layers are not supported (every layer is sparse)")
     if (getattr(hf_config, "shared_expert_intermediate_size", 0) or getattr(hf_config, "n_shared_experts", 0)

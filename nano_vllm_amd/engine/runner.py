@@ -356,7 +356,8 @@ class ModelRunner:
         min(NVL_PACKED_BUDGET_FRAC (default 0.25) x device memory, half of what is free once the weights are loaded);
         projections are packed in model order until the next one no longer fits, the rest keep the row-major weight
         stream (slower decode GEMM, same results bit for bit) — on a 192 GB part Qwen3-32B packs its first ~48 GB and
-        keeps its KV pool. weight_dtype="mxfp4" replaces the MoE blocks' expert matrices by their 4-bit form instead.
+        keeps its KV pool. weight_dtype="mxfp4" replaces the MoE blocks' expert matrices by their 4-bit form instead, and
+        weight_dtype="fp8_only" the dense projections by their e4m3 tiles (half of bf16's bytes, no second copy).
         Returns (bytes packed or quantised, projections left unpacked for lack of budget)."""
         from ..layers import LinearBase, ParallelLMHead
         free, total = torch.cuda.mem_get_info(self.device)
@@ -375,6 +376,9 @@ class ModelRunner:
             if isinstance(m, (LinearBase, ParallelLMHead)):
                 if isinstance(m, LinearBase):      # (lm_head and embedding stay bf16, as in the published FP8 checkpoints)
                     got = m.pack_for_decode(budget - used, weight_dtype=self.config.weight_dtype)
+                    if m.weight_released:          # "fp8_only": quantised in place of the bf16 parameter, as mxfp4
+                        quantised += got           # above — reported, not budgeted (the KV pool is sized from what
+                        continue                   # is free after the warm-up's empty_cache())
                 else:
                     got = m.pack_for_decode(budget - used)
                 if got < 0:

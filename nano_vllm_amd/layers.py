@@ -263,6 +263,8 @@ class LinearBase(nn.Module):
         self.weight_packed: torch.Tensor | None = None     # tile-packed copy for nvl_linear_wide (pack_for_decode)
         self.weight_fp8_packed: torch.Tensor | None = None # e4m3 tile-packed copy + its [N/16, K/128] fp32 scales for
         self.weight_scale: torch.Tensor | None = None      # nvl_linear_wide_fp8 (pack_for_decode(weight_dtype="fp8"))
+        self.nk = (output_size, input_size)                # this rank's (n, k): survives the release of `weight`
+        self.weight_released = False                       # weight_dtype="fp8_only": the bf16 storage is gone
 
     def _pack_fp8(self, budget_bytes: float) -> int | None:
         """weight_dtype="fp8": quantise this rank's weight as loaded (the merged q|k|v / gate|up matrix) in 128 x 128
@@ -299,7 +301,9 @@ class LinearBase(nn.Module):
         GEMM is one of the hand-written kernels — the skinny kernel (K <= 1024-3072: Qwen3-0.6B) or the wide-tile one
         (deep reductions: Qwen3-8B / 32B shapes). The row-major parameter stays: prefill-sized GEMMs run on hipBLASLt
         from it. Returns the extra bytes (0: shape not covered; -1: covered, but the copy does not fit `budget_bytes`
-        — ModelRunner._pack_weights). NVL_PACKED_WEIGHTS=0 keeps the row-major weight stream (A/B measurements)."""
+        — ModelRunner._pack_weights). NVL_PACKED_WEIGHTS=0 keeps the row-major weight stream (A/B measurements).
+        weight_dtype="fp8_only": as "fp8", then the row-major parameter is RELEASED (`weight.numel() == 0`, `nk` keeps
+        its shape) — every row count runs on the e4m3 tiles (`_released_linear`); returns the bytes of tiles + scales."""
         n, k = self.weight.shape
         if (self.bias is not None or not self.weight.is_cuda or n % 16 or k % 32
                 or os.environ.get("NVL_PACKED_WEIGHTS", "1") == "0"):
@@ -307,6 +311,15 @@ class LinearBase(nn.Module):
         if weight_dtype == "fp8":
             got = self._pack_fp8(budget_bytes)
             if got is not None:
+                return got
+        if weight_dtype == "fp8_only":
+            # the same quantisation, then the bf16 storage is RELEASED: nvl_linear_tile_fp8 serves the row counts the
+            # library GEMM read it for. The call frees more than it takes, so the budget does not apply; a projection
+            # the fp8 path cannot take keeps its parameter and the bf16 paths below.
+            got = self._pack_fp8(float("inf"))
+            if got is not None:
+                self.weight.data = torch.empty(0, dtype=self.weight.dtype, device=self.weight.device)
+                self.weight_released = True
                 return got
         skinny = any(ops.linear_decode_splits(144, n, k, mode) for mode in (ops.LINEAR_BF16, ops.LINEAR_PARTIAL))
         wide = (k % 128 == 0 and os.environ.get("NVL_GEMM_WIDE", "auto") != "0"
@@ -322,6 +335,23 @@ class LinearBase(nn.Module):
         """(e4m3 tile-packed weight, scales) of a projection packed with weight_dtype="fp8", else None."""
         return None if self.weight_fp8_packed is None else (self.weight_fp8_packed, self.weight_scale)
 
+    def _released_linear(self, x: torch.Tensor, mode: int) -> torch.Tensor:
+        """x . W^T of a projection whose bf16 parameter was released (weight_dtype="fp8_only"): nvl_linear_wide_fp8
+        wherever its plan covers (rows, n, k, mode) — the decode behaviour of "fp8" — and nvl_linear_tile_fp8
+        everywhere else (every row count above 256; a slab request the plan refuses becomes a bf16 output). There is
+        no library GEMM behind this: what neither kernel takes raises NvlError."""
+        n, k = self.nk
+        if not (x.dim() == 2 and x.shape[1] == k and x.dtype == torch.bfloat16 and x.is_cuda):
+            raise ops.NvlError(f"fp8_only projection [{n}, {k}]: input {tuple(x.shape)} {x.dtype} on {x.device} is not covered")
+        x = x.contiguous()
+        if x.shape[0] <= DECODE_LINEAR_MAX_ROWS:
+            plan = ops.linear_wide_fp8_plan(x.shape[0], n, k, mode)
+            if plan is not None:
+                return ops.linear_wide_fp8(x, self.weight_fp8_packed, self.weight_scale, mode,
+                                           workspace=_scratch(plan[1], x.device))
+        return ops.linear_tile_fp8(x, self.weight_fp8_packed, self.weight_scale,
+                                   ops.LINEAR_BF16 if mode == ops.LINEAR_PARTIAL else mode)
+
     def _my_slice(self, loaded: torch.Tensor, dim: int) -> torch.Tensor:
         size = loaded.shape[dim] // self.tp_size
         return loaded.narrow(dim, self.tp_rank * size, size)
@@ -330,6 +360,8 @@ class LinearBase(nn.Module):
         raise NotImplementedError
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.weight_released:
+            return self._released_linear(x, ops.LINEAR_BF16)
         if self.bias is None and _decode_sized(x):
             y = decode_linear(x, self.weight, ops.LINEAR_BF16, packed=self.weight_packed, fp8=self._fp8())
             if y is not None:
@@ -453,7 +485,7 @@ def decode_linear(x: torch.Tensor, weight: torch.Tensor, mode: int, out: torch.T
     module's (e4m3 tile-packed weight, scales) — then nvl_linear_wide_fp8 takes every shape its plan covers (a shape
     rule: no timing decides), and the rest falls through to the bf16 paths on the dequantised `weight`."""
     m, k = x.shape
-    n = weight.shape[0]
+    n = weight.shape[0] if fp8 is None else fp8[0].shape[0]         # (a released parameter has no shape: "fp8_only")
     if fp8 is not None:
         plan = ops.linear_wide_fp8_plan(m, n, k, mode)
         if plan is not None:
@@ -504,7 +536,9 @@ class MergedColumnParallelLinear(ColumnParallelLinear):
 
     def forward_silu(self, x: torch.Tensor) -> torch.Tensor:
         """SiluAndMul(self(x)) for a gate|up pair; on decode-sized inputs the activation is the GEMM's
-        epilogue (one launch, no [N, 2*inter] round trip)."""
+        epilogue (one launch, no [N, 2*inter] round trip) — with weight_dtype="fp8_only" at every row count."""
+        if self.weight_released:
+            return self._released_linear(x, ops.LINEAR_SILU)
         if (self.bias is None and len(self.output_sizes) == 2 and self.output_sizes[0] == self.output_sizes[1]
                 and _decode_sized(x)):
             y = decode_linear(x, self.weight, ops.LINEAR_SILU, packed=self.weight_packed, fp8=self._fp8())
@@ -542,7 +576,7 @@ class QKVParallelLinear(ColumnParallelLinear):
         if (_QKV_SLABS and self.bias is None and _decode_sized(x)
                 and ops.decode_attention_takes_qkv_slabs(self.num_heads, self.num_kv_heads)):
             m, k = x.shape
-            n = self.weight.shape[0]
+            n = self.nk[0]
             if self.weight_fp8_packed is not None:                           # fp8 weights: the same hand-off, by the fp8 plan
                 plain = ops.linear_wide_fp8_plan(m, n, k, ops.LINEAR_BF16)
                 slabs = ops.linear_wide_fp8_plan(m, n, k, ops.LINEAR_PARTIAL) if plain else None
@@ -590,8 +624,10 @@ class RowParallelLinear(LinearBase):
                   prologue);
           TP > 1, message fits the P2P comm buffer: this rank's bf16 partial sums as `PartialSum` (the xGMI
                   all-reduce is fused with the residual-add + RMSNorm)."""
-        n, k = self.weight.shape
+        n, k = self.nk
         if self.tp_size == 1:
+            if self.weight_released:
+                return self._released_linear(x, ops.LINEAR_PARTIAL)
             if self.bias is None and _decode_sized(x):
                 y = decode_linear(x, self.weight, ops.LINEAR_PARTIAL, packed=self.weight_packed, fp8=self._fp8())
                 if y is not None:

@@ -36,6 +36,7 @@ SIGNATURES = {
     "nvl_linear_wide_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_size_t,
                                     c_void_p]),
     "nvl_pack_weight_tiles_fp8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "nvl_linear_tile_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "nvl_add_rmsnorm_splitk": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p]),
     "nvl_silu_mul": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
     "nvl_moe_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
@@ -332,6 +333,26 @@ def linear_wide_fp8(x: torch.Tensor, w8_packed: torch.Tensor, scales: torch.Tens
     assert not ws_bytes or workspace.numel() * workspace.element_size() >= ws_bytes
     _check(lib().nvl_linear_wide_fp8(x.data_ptr(), w8_packed.data_ptr(), scales.data_ptr(), out.data_ptr(), m, n, k, mode,
                                      workspace.data_ptr() if ws_bytes else None, ws_bytes, _stream()))
+    return out
+
+
+def linear_tile_fp8(x: torch.Tensor, w8_packed: torch.Tensor, scales: torch.Tensor, mode: int = LINEAR_BF16,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """x [M, K] bf16 . (w8 o scales)^T for ANY M (nvl_linear_tile_fp8): operands as linear_wide_fp8, scales powers of two
+    (include/nvl.h). mode LINEAR_BF16 -> bf16 [M, N], LINEAR_SILU -> bf16 [M, N/2]; LINEAR_PARTIAL is not offered. `out`
+    may have more than M rows: the rows past M are left untouched."""
+    _dev(x, "x")
+    assert x.dim() == 2 and x.is_contiguous() and w8_packed.is_contiguous() and scales.is_contiguous()
+    assert x.dtype == torch.bfloat16 and w8_packed.dtype == torch.float8_e4m3fn and scales.dtype == torch.float32
+    m, k = x.shape
+    n = w8_packed.shape[0]
+    assert w8_packed.shape[1] == k and scales.shape == (n // 16, k // 128)
+    cols = n // 2 if mode == LINEAR_SILU else n
+    if out is None:
+        out = torch.empty((m, cols), dtype=torch.bfloat16, device=x.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape[0] >= m and out.shape[1] == cols
+    _check(lib().nvl_linear_tile_fp8(x.data_ptr(), w8_packed.data_ptr(), scales.data_ptr(), out.data_ptr(), m, n, k, mode,
+                                     _stream()))
     return out
 
 

@@ -5,8 +5,18 @@ at 16 / 64 / 144 / 256 rows. Writes a JSON table (us, achieved weight GB/s, the 
     python tools/gemm_fp8_bench.py [--out profiles/fp8_gemm_wide_vs_bf16.json] [--engine]
 
 --engine adds one engine-level pair: qwen3-8b dummy weights, 256 sequences, weight_dtype bf16 against fp8, LLM.generate.
+
+--tile is a leg of its own (the wide-kernel table is not re-measured): nvl_linear_tile_fp8 against the path the same rows
+take with weight_dtype="fp8" — F.linear on the dequantised bf16 weight, plus the silu_mul launch for gate|up — on every
+full-width Qwen3-8B / 32B projection at 512 / 2048 / 8192 / 16384 rows. Caches warm, the way consecutive prefill GEMMs see
+them; the two paths alternate, each sample is a run of back-to-back calls long enough (>= 5 ms) for the device events, best
+of 5. With --engine it adds "fp8" against "fp8_only": tok/s on qwen3-8b (256 sequences), and resident weight bytes + KV
+blocks of qwen3-32b dummy weights.
+
+    python tools/gemm_fp8_bench.py --tile [--engine] [--out profiles/fp8_only_tile_vs_library.json]
 """
 import argparse
+import gc
 import json
 import os
 import sys
@@ -65,7 +75,84 @@ def refit(rows):
     return dict(w_gbs_per_cu=round(1e-3 / sol[0], 2) if sol[0] > 0 else None, x_gbs_per_cu=round(1e-3 / sol[1], 2) if sol[1] > 0 else None)
 
 
-def bench_engine():
+TILE_ROWS = (512, 2048, 8192, 16384)
+
+
+def _best_of(fns, dev, samples=5, window_ms=5.0):
+    """Best-of-`samples` time (us per call) of each fn, warm: samples alternate between the fns; one sample is `reps` calls
+    back to back between two events, `reps` sized from a first timed call so that the window is >= window_ms."""
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(fn, reps):
+        start.record()
+        for _ in range(reps):
+            fn()
+        stop.record()
+        stop.synchronize()
+        return start.elapsed_time(stop) / reps
+    reps = []
+    for fn in fns:
+        fn()                                          # warm-up: code object, library heuristics, allocator
+        reps.append(max(1, int(window_ms / max(window(fn, 1), 1e-3))))
+    best = [float("inf")] * len(fns)
+    for _ in range(samples):
+        for i, fn in enumerate(fns):
+            best[i] = min(best[i], window(fn, reps[i]))
+    return [b * 1e3 for b in best]
+
+
+def bench_tile():
+    import torch.nn.functional as F
+    dev = torch.device("cuda")
+    rows = []
+    for model, tp, proj, n, k, mode in shapes():
+        if tp != 1:
+            continue
+        mode = ops.LINEAR_SILU if proj == "gate_up" else ops.LINEAR_BF16          # (no slabs at these row counts)
+        w8 = (torch.randn(n, k, device=dev) * 0.05).to(torch.float8_e4m3fn)
+        sc = torch.exp2(torch.randint(-8, -3, (n // 16, k // 128), device=dev).float())
+        wd = (w8.to(torch.bfloat16).view(n // 16, 16, k // 128, 128) * sc.to(torch.bfloat16)[:, None, :, None]).view(n, k)
+        w8p = ops.pack_weight_tiles_fp8(w8)
+        del w8
+        for m in TILE_ROWS:
+            x = (torch.randn(m, k, device=dev) * 0.5).to(torch.bfloat16)
+            out = ops.linear_tile_fp8(x, w8p, sc, mode)
+            lib = (lambda: ops.silu_mul(F.linear(x, wd))) if mode == ops.LINEAR_SILU else (lambda: F.linear(x, wd))
+            same = float((out.float() - lib().float()).abs().max()) / float(out.float().abs().max())
+            t_tile, t_lib = _best_of([lambda: ops.linear_tile_fp8(x, w8p, sc, mode, out=out), lib], dev)
+            rows.append(dict(model=model, proj=proj, n=n, k=k, mode=mode, m=m, tile_us=round(t_tile, 1), library_us=round(t_lib, 1),
+                             tile_tflops=round(2.0 * m * n * k / t_tile / 1e6, 1), library_tflops=round(2.0 * m * n * k / t_lib / 1e6, 1),
+                             library_over_tile=round(t_lib / t_tile, 3), max_rel_diff=round(same, 5)))
+            print(json.dumps(rows[-1]), flush=True)
+            del x, out
+        del wd, w8p
+    return rows
+
+
+def engine_memory(model="qwen3-32b"):
+    """Resident bytes and KV blocks of `model` (dummy weights, eager) with "fp8" and with "fp8_only"."""
+    from nano_vllm_amd import LLM
+    from nano_vllm_amd.weights import write_synthetic_checkpoint
+    path = tempfile.mkdtemp(prefix=model.replace("-", "_") + "_")
+    write_synthetic_checkpoint(path, model, with_weights=False)
+    out = {}
+    for dt in ("fp8", "fp8_only"):
+        llm = LLM(path, dummy_weights=True, max_model_len=4096, enforce_eager=True, weight_dtype=dt)
+        r = llm.model_runner
+        proj = sum(m.weight.numel() * 2 + m.weight_fp8_packed.numel() + m.weight_scale.numel() * 4
+                   for m in r.model.modules() if isinstance(m, layers.LinearBase) and m.weight_fp8_packed is not None)
+        out[dt] = dict(projection_bytes_resident=proj, packed_weight_bytes=r.packed_weight_bytes,
+                       model_bytes_allocated=torch.cuda.memory_allocated() - r._kv_storage.numel() * r._kv_storage.element_size(),
+                       kv_blocks=llm.config.num_kvcache_blocks, kv_block_tokens=r.block_size)
+        llm.exit()
+        del llm, r
+        gc.collect()                                  # (parameter <-> weight_loader cycles: the model is freed by the collector)
+        torch.cuda.empty_cache()
+        print(json.dumps({dt: out[dt]}), flush=True)
+    return out
+
+
+def bench_engine(dtypes=("bf16", "fp8")):
     from nano_vllm_amd import LLM, SamplingParams
     from nano_vllm_amd.weights import write_synthetic_checkpoint
     path = tempfile.mkdtemp(prefix="qwen3_8b_")
@@ -74,7 +161,7 @@ def bench_engine():
     prompts = [torch.randint(0, 10000, (int(torch.randint(100, 1024, (1,), generator=g)),), generator=g).tolist() for _ in range(256)]
     sp = SamplingParams(temperature=0.6, max_tokens=128, ignore_eos=True)
     out = {}
-    for dt in ("bf16", "fp8"):
+    for dt in dtypes:
         llm = LLM(path, dummy_weights=True, max_model_len=4096, max_num_seqs=256, weight_dtype=dt)
         llm.generate(prompts[:8], SamplingParams(temperature=0.6, max_tokens=8, ignore_eos=True), use_tqdm=False)
         torch.cuda.synchronize()
@@ -86,6 +173,7 @@ def bench_engine():
                        packed_weight_bytes=llm.model_runner.packed_weight_bytes)
         llm.exit()
         del llm
+        gc.collect()
         torch.cuda.empty_cache()
         print(json.dumps({dt: out[dt]}), flush=True)
     return out
@@ -93,9 +181,21 @@ def bench_engine():
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/fp8_gemm_wide_vs_bf16.json")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--engine", action="store_true")
+    ap.add_argument("--tile", action="store_true")
     args = ap.parse_args()
+    if args.tile:
+        args.out = args.out or "profiles/fp8_only_tile_vs_library.json"
+        result = dict(tile=bench_tile())
+        if args.engine:
+            result["engine_qwen3_8b_256seq"] = bench_engine(("fp8", "fp8_only"))
+            result["memory_qwen3_32b"] = engine_memory()
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+        sys.exit(0)
+    args.out = args.out or "profiles/fp8_gemm_wide_vs_bf16.json"
     table = bench_gemms()
     result = dict(gemm=table, refit_fp8=refit(table))
     if args.engine:
