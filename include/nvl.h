@@ -233,6 +233,34 @@ int nvl_moe_experts_mxfp4(const void* x, const void* gu_codes, const void* gu_sc
                           int hidden, int inter, int E, int top_k, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* MXFP4 weights for the DENSE decode projections (opt-in: LLM(..., weight_dtype="mxfp4_dense"); csrc/gemm_wide_mxfp4.hip):
+ * the W4A16 variant of nvl_linear_wide over the format above,
+ *   out[m, n] = x[m, k] (bf16) . W_deq[n, k]^T,  W_deq = e2m1 code x 2^(scale byte - 127), one scale per row and 32 k.
+ * Modes 0 / 1 / 2, output shapes, slab conventions and rounding points are nvl_linear_wide's. m = 1 ... 256,
+ * n % 16 == 0 (mode 1: n % 32 == 0), k % 128 == 0, m * k < 2^31; fp32 accumulation on v_mfma_f32_16x16x32_bf16.
+ *   codes:        uint8 [n/16][k/128][64 lanes][16 bytes], exactly what nvl_quant_pack_mxfp4 writes.
+ *   scales_tiled: uint8 [n/16][k/128][16 rows][4 k blocks] — the quantiser's row-major [n][k/32] bytes re-laid so that
+ *                 the scales of a (16-row tile, 128-wide k step) are one 64-byte line: byte ((t * k/128 + s) * 16 + r) * 4
+ *                 + b is scales[16 t + r][4 s + b].
+ * EXACTNESS: the matrix instruction receives bf16(code x scale). For every scale byte for which code x scale is a normal
+ * bf16 (bytes 2 ... 252 for every code; byte 1 for every code but 0.5, whose product 2^-127 is a bf16 subnormal) that
+ * conversion is exact, so the result is x . W_deq^T up to the fp32 summation order. Outside that range nothing is
+ * promised: a subnormal product is whatever v_cvt_scalef32_pk_bf16_fp4 and the matrix instruction make of it (it may be
+ * flushed to zero), byte 0 reads as scale 0, bytes 253 ... 255 overflow to infinity for the larger codes. The quantiser
+ * emits byte 1 only for blocks whose largest magnitude is below 2^-123, i.e. never for real weights.
+ *   nvl_linear_wide_mxfp4_plan: as nvl_linear_wide_fp8_plan (pure host code): 1 / 0, *splits, *workspace_bytes
+ *     (modes 0 / 1 with a K split: splits * m * n * 4).
+ *   nvl_linear_wide_mxfp4: NVL_EUNSUPPORTED ("not covered") when the plan query says 0; NVL_EINVAL on null or
+ *     misaligned (16 bytes) pointers, a bad mode or a short workspace, all checked on the host before any launch. The
+ *     first call of a 7- or 9-row-tile shape on a device opts its kernel into > 64 KiB of LDS (hipFuncSetAttribute):
+ *     make it before any capture.
+ *   nvl_unpack_mxfp4: inverse of nvl_quant_pack_mxfp4 (its codes, its ROW-MAJOR scales): writes the dequantised
+ *     row-major bf16 [n, k] matrix, bit for bit the W_deq above. n % 16 == 0, k % 128 == 0, 16-byte-aligned pointers. */
+int nvl_linear_wide_mxfp4_plan(int64_t m, int n, int k, int mode, int* splits, size_t* workspace_bytes);
+int nvl_linear_wide_mxfp4(const void* x, const void* codes, const void* scales_tiled, void* out, int64_t m, int n, int k,
+                          int mode, void* workspace, size_t workspace_bytes, void* stream);
+int nvl_unpack_mxfp4(const void* codes, const void* scales, void* w_bf16_out, int64_t n, int64_t k, void* stream);
+
 /* ---- Rotary embedding -----------------------------------------------------
  * Replaces RotaryEmbedding.forward / apply_rotary_emb
  * (layers/rotary_embedding.py:6-14, 37-48): neox (half-split) rotation from a

@@ -358,6 +358,8 @@ class ModelRunner:
         stream (slower decode GEMM, same results bit for bit) — on a 192 GB part Qwen3-32B packs its first ~48 GB and
         keeps its KV pool. weight_dtype="mxfp4" replaces the MoE blocks' expert matrices by their 4-bit form instead, and
         weight_dtype="fp8_only" the dense projections by their e4m3 tiles (half of bf16's bytes, no second copy).
+        weight_dtype="mxfp4_dense" keeps the bf16 parameters and budgets the MXFP4 codes + scales (17/32 byte per weight)
+        like the packed copies they replace.
         Returns (bytes packed or quantised, projections left unpacked for lack of budget)."""
         from ..layers import LinearBase, ParallelLMHead
         free, total = torch.cuda.mem_get_info(self.device)

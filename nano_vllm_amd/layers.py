@@ -263,6 +263,8 @@ class LinearBase(nn.Module):
         self.weight_packed: torch.Tensor | None = None     # tile-packed copy for nvl_linear_wide (pack_for_decode)
         self.weight_fp8_packed: torch.Tensor | None = None # e4m3 tile-packed copy + its [N/16, K/128] fp32 scales for
         self.weight_scale: torch.Tensor | None = None      # nvl_linear_wide_fp8 (pack_for_decode(weight_dtype="fp8"))
+        self.weight_mxfp4: tuple | None = None             # (codes, tile-major scales) for nvl_linear_wide_mxfp4
+        #                                                    (pack_for_decode(weight_dtype="mxfp4_dense"))
         self.nk = (output_size, input_size)                # this rank's (n, k): survives the release of `weight`
         self.weight_released = False                       # weight_dtype="fp8_only": the bf16 storage is gone
 
@@ -296,6 +298,24 @@ class LinearBase(nn.Module):
         self.weight_scale = scale.repeat_interleave(8, 0)[:n // 16].contiguous()
         return n * k + self.weight_scale.numel() * 4
 
+    def _pack_mxfp4(self, budget_bytes: float) -> int | None:
+        """weight_dtype="mxfp4_dense": quantise this rank's weight as loaded to OCP MXFP4 (ops.quant_pack_mxfp4: e2m1
+        codes, one power-of-two scale byte per row and 32 k — per row, so a merged q|k|v / gate|up matrix quantises
+        exactly as its parts would), OVERWRITE the bf16 parameter in place with the dequantised values
+        (nvl_unpack_mxfp4: code x scale is a bf16 value, so the prefill-sized library GEMM and the decode kernel compute
+        with one and the same matrix) and keep the codes + tile-major scales (n k 17/32 bytes) instead of the bf16 packed
+        copy. None: shape not covered by nvl_linear_wide_mxfp4 (the projection keeps today's path)."""
+        n, k = self.weight.shape
+        if k % 128 or ops.linear_wide_mxfp4_plan(144, n, k, ops.LINEAR_BF16) is None:
+            return None
+        nbytes = n * k // 2 + n * (k // 32)
+        if nbytes > budget_bytes:
+            return -1
+        codes, scales = ops.quant_pack_mxfp4(self.weight.data)
+        ops.unpack_mxfp4(codes, scales, out=self.weight.data)
+        self.weight_mxfp4 = (codes, ops.tile_scales_mxfp4(scales))
+        return nbytes
+
     def pack_for_decode(self, budget_bytes: float = float("inf"), weight_dtype: str = "bf16") -> int:
         """After the weights are loaded: keep a tile-packed copy (ops.pack_weight_tiles) of a projection whose decode
         GEMM is one of the hand-written kernels — the skinny kernel (K <= 1024-3072: Qwen3-0.6B) or the wide-tile one
@@ -310,6 +330,10 @@ class LinearBase(nn.Module):
             return 0
         if weight_dtype == "fp8":
             got = self._pack_fp8(budget_bytes)
+            if got is not None:
+                return got
+        if weight_dtype == "mxfp4_dense":
+            got = self._pack_mxfp4(budget_bytes)
             if got is not None:
                 return got
         if weight_dtype == "fp8_only":
@@ -363,7 +387,8 @@ class LinearBase(nn.Module):
         if self.weight_released:
             return self._released_linear(x, ops.LINEAR_BF16)
         if self.bias is None and _decode_sized(x):
-            y = decode_linear(x, self.weight, ops.LINEAR_BF16, packed=self.weight_packed, fp8=self._fp8())
+            y = decode_linear(x, self.weight, ops.LINEAR_BF16, packed=self.weight_packed, fp8=self._fp8(),
+                              mxfp4=self.weight_mxfp4)
             if y is not None:
                 return y
         return F.linear(x, self.weight, self.bias)
@@ -478,14 +503,19 @@ def _use_wide(x: torch.Tensor, weight: torch.Tensor, mode: int, packed: torch.Te
 
 
 def decode_linear(x: torch.Tensor, weight: torch.Tensor, mode: int, out: torch.Tensor | None = None,
-                  packed: torch.Tensor | None = None, fp8: tuple | None = None):
+                  packed: torch.Tensor | None = None, fp8: tuple | None = None, mxfp4: tuple | None = None):
     """x [M, K] . weight[N, K]^T on a hand-written decode GEMM, or None when neither kernel takes the shape (the
     caller keeps the library GEMM). mode as in ops.linear_decode. `packed`: the module's tile-packed copy of
     `weight` (LinearBase.pack_for_decode), streamed by the wide kernel instead of the row-major parameter. `fp8`: the
     module's (e4m3 tile-packed weight, scales) — then nvl_linear_wide_fp8 takes every shape its plan covers (a shape
-    rule: no timing decides), and the rest falls through to the bf16 paths on the dequantised `weight`."""
+    rule: no timing decides), and the rest falls through to the bf16 paths on the dequantised `weight`. `mxfp4`: the
+    module's (MXFP4 codes, tile-major scales) — nvl_linear_wide_mxfp4 by the same shape rule."""
     m, k = x.shape
     n = weight.shape[0] if fp8 is None else fp8[0].shape[0]         # (a released parameter has no shape: "fp8_only")
+    if mxfp4 is not None:
+        plan = ops.linear_wide_mxfp4_plan(m, n, k, mode)
+        if plan is not None:
+            return ops.linear_wide_mxfp4(x, mxfp4[0], mxfp4[1], mode, out=out, workspace=_scratch(plan[1], x.device))
     if fp8 is not None:
         plan = ops.linear_wide_fp8_plan(m, n, k, mode)
         if plan is not None:
@@ -541,7 +571,8 @@ class MergedColumnParallelLinear(ColumnParallelLinear):
             return self._released_linear(x, ops.LINEAR_SILU)
         if (self.bias is None and len(self.output_sizes) == 2 and self.output_sizes[0] == self.output_sizes[1]
                 and _decode_sized(x)):
-            y = decode_linear(x, self.weight, ops.LINEAR_SILU, packed=self.weight_packed, fp8=self._fp8())
+            y = decode_linear(x, self.weight, ops.LINEAR_SILU, packed=self.weight_packed, fp8=self._fp8(),
+                              mxfp4=self.weight_mxfp4)
             if y is not None:
                 return y
         return ops.silu_mul(self.forward(x))
@@ -582,6 +613,15 @@ class QKVParallelLinear(ColumnParallelLinear):
                 slabs = ops.linear_wide_fp8_plan(m, n, k, ops.LINEAR_PARTIAL) if plain else None
                 if plain and plain[0] > 1 and slabs and slabs[0] <= 8:
                     return decode_linear(x, self.weight, ops.LINEAR_PARTIAL, fp8=self._fp8())
+                return self.forward(x)
+            # MXFP4 weights: likewise, by their plan. As on the fp8 branch the slab plan may split K differently from the
+            # bf16 plan (Qwen3-8B qkv at one row: 8 against 16 ways), so the hand-off gives forward()'s value up to the
+            # fp32 summation order, not its bits; which of the two a shape takes is fixed by the shape, in every run.
+            if self.weight_mxfp4 is not None:
+                plain = ops.linear_wide_mxfp4_plan(m, n, k, ops.LINEAR_BF16)
+                slabs = ops.linear_wide_mxfp4_plan(m, n, k, ops.LINEAR_PARTIAL) if plain else None
+                if plain and plain[0] > 1 and slabs and slabs[0] <= 8:
+                    return decode_linear(x, self.weight, ops.LINEAR_PARTIAL, mxfp4=self.weight_mxfp4)
                 return self.forward(x)
             if not ops.linear_decode_splits(m, n, k, ops.LINEAR_BF16):       # (the skinny kernel never leaves slabs)
                 plain = ops.linear_wide_plan(m, n, k, ops.LINEAR_BF16) if k % 128 == 0 else None
@@ -629,7 +669,8 @@ class RowParallelLinear(LinearBase):
             if self.weight_released:
                 return self._released_linear(x, ops.LINEAR_PARTIAL)
             if self.bias is None and _decode_sized(x):
-                y = decode_linear(x, self.weight, ops.LINEAR_PARTIAL, packed=self.weight_packed, fp8=self._fp8())
+                y = decode_linear(x, self.weight, ops.LINEAR_PARTIAL, packed=self.weight_packed, fp8=self._fp8(),
+                                  mxfp4=self.weight_mxfp4)
                 if y is not None:
                     return y
             return self.forward(x)
@@ -639,7 +680,7 @@ class RowParallelLinear(LinearBase):
             # then starts at its first flag instead of a copy-in phase
             buf = c.input_buffer(x.shape[0], n, x.device)
             if not _decode_sized(x) or decode_linear(x, self.weight, ops.LINEAR_BF16, out=buf, packed=self.weight_packed,
-                                                          fp8=self._fp8()) is None:
+                                                          fp8=self._fp8(), mxfp4=self.weight_mxfp4) is None:
                 torch.mm(x, self.weight.t(), out=buf)
             return PartialSum(buf)
         return self.forward(x)

@@ -47,6 +47,10 @@ SIGNATURES = {
     "nvl_quant_pack_mxfp4": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "nvl_moe_experts_mxfp4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_int64, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "nvl_linear_wide_mxfp4_plan": (c_int, [c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "nvl_linear_wide_mxfp4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_size_t,
+                                      c_void_p]),
+    "nvl_unpack_mxfp4": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "nvl_rope_neox": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "nvl_store_kvcache": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64,
                                   c_int, c_void_p]),
@@ -463,6 +467,69 @@ def moe_experts_mxfp4(x: torch.Tensor, gu: torch.Tensor, gu_scales: torch.Tensor
     _check(lib().nvl_moe_experts_mxfp4(x.data_ptr(), gu.data_ptr(), gu_scales.data_ptr(), dn.data_ptr(), dn_scales.data_ptr(),
                                        ids.data_ptr(), weights.data_ptr(), out.data_ptr(), m, hidden, inter, e, ids.shape[1],
                                        workspace.data_ptr(), workspace.numel(), _stream()))
+    return out
+
+
+# ---- weight-only MXFP4 (W4A16) wide linears for the dense projections: quant_pack_mxfp4's codes, tile-major scales -------
+_wide_mxfp4_cache: dict = {}
+
+
+def linear_wide_mxfp4_plan(m: int, n: int, k: int, mode: int) -> tuple[int, int] | None:
+    """(K splits, workspace bytes) of nvl_linear_wide_mxfp4's plan for this shape, or None when it is not covered."""
+    key = (m, n, k, mode)
+    if key not in _wide_mxfp4_cache:
+        splits, ws = ctypes.c_int(0), ctypes.c_size_t(0)
+        ok = lib().nvl_linear_wide_mxfp4_plan(m, n, k, mode, ctypes.byref(splits), ctypes.byref(ws))
+        _wide_mxfp4_cache[key] = (splits.value, ws.value) if ok else None
+    return _wide_mxfp4_cache[key]
+
+
+def tile_scales_mxfp4(scales: torch.Tensor) -> torch.Tensor:
+    """quant_pack_mxfp4's row-major scale bytes [N, K/32] -> the tile-major [N/16, K/128, 16, 4] nvl_linear_wide_mxfp4
+    reads (a tile step's scales are one 64-byte line). Done once at load."""
+    n, kb = scales.shape
+    assert scales.dtype == torch.uint8 and n % 16 == 0 and kb % 4 == 0
+    return scales.view(n // 16, 16, kb // 4, 4).permute(0, 2, 1, 3).contiguous()
+
+
+def unpack_mxfp4(codes: torch.Tensor, scales: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Inverse of quant_pack_mxfp4 (its codes and ROW-MAJOR scales [N, K/32]): the dequantised bf16 [N, K] matrix
+    (nvl_unpack_mxfp4), written into `out` when given."""
+    _dev(codes, "codes")
+    assert codes.is_contiguous() and scales.is_contiguous() and codes.dtype == torch.uint8 and scales.dtype == torch.uint8
+    n, k = scales.shape[0], scales.shape[1] * 32
+    assert scales.dim() == 2 and codes.numel() * 2 == n * k
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.bfloat16, device=codes.device)
+    assert out.shape == (n, k) and out.dtype == torch.bfloat16 and out.is_contiguous()
+    _check(lib().nvl_unpack_mxfp4(codes.data_ptr(), scales.data_ptr(), out.data_ptr(), n, k, _stream()))
+    return out
+
+
+def linear_wide_mxfp4(x: torch.Tensor, codes: torch.Tensor, scales_tiled: torch.Tensor, mode: int = LINEAR_BF16,
+                      out: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """x [M, K] bf16 . W_deq^T over MXFP4 weights: `codes` from quant_pack_mxfp4 ([N/16, K/128, 64, 16]), `scales_tiled`
+    from tile_scales_mxfp4 ([N/16, K/128, 16, 4]). Modes, outputs and `workspace` as linear_wide."""
+    _dev(x, "x")
+    assert x.dim() == 2 and x.is_contiguous() and codes.is_contiguous() and scales_tiled.is_contiguous()
+    assert x.dtype == torch.bfloat16 and codes.dtype == torch.uint8 and scales_tiled.dtype == torch.uint8
+    m, k = x.shape
+    n = codes.shape[0] * 16
+    assert tuple(codes.shape) == (n // 16, k // 128, 64, 16) and tuple(scales_tiled.shape) == (n // 16, k // 128, 16, 4)
+    plan = linear_wide_mxfp4_plan(m, n, k, mode)
+    if plan is None:
+        raise NvlError(f"nvl_linear_wide_mxfp4 does not cover m={m} n={n} k={k} mode={mode}")
+    splits, ws_bytes = plan
+    if out is None:
+        if mode == LINEAR_PARTIAL:
+            out = torch.empty((splits, m, n), dtype=torch.float32, device=x.device)
+        else:
+            out = torch.empty((m, n // 2 if mode == LINEAR_SILU else n), dtype=torch.bfloat16, device=x.device)
+    if ws_bytes and workspace is None:
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    assert not ws_bytes or workspace.numel() * workspace.element_size() >= ws_bytes
+    _check(lib().nvl_linear_wide_mxfp4(x.data_ptr(), codes.data_ptr(), scales_tiled.data_ptr(), out.data_ptr(), m, n, k, mode,
+                                       workspace.data_ptr() if ws_bytes else None, ws_bytes, _stream()))
     return out
 
 

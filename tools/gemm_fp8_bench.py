@@ -14,6 +14,13 @@ of 5. With --engine it adds "fp8" against "fp8_only": tok/s on qwen3-8b (256 seq
 blocks of qwen3-32b dummy weights.
 
     python tools/gemm_fp8_bench.py --tile [--engine] [--out profiles/fp8_only_tile_vs_library.json]
+
+--mxfp4 is a leg of its own as well: nvl_linear_wide_mxfp4 (weight_dtype="mxfp4_dense") against nvl_linear_wide (bf16
+tile-packed) and nvl_linear_wide_fp8 on every full-width Qwen3-8B / 32B projection at 1 / 16 / 64 / 144 / 256 rows, cold L2 /
+MALL before every sample, best of 5. With --engine it adds resident projection bytes + KV blocks of qwen3-32b dummy
+weights with "bf16", "fp8" and "mxfp4_dense".
+
+    python tools/gemm_fp8_bench.py --mxfp4 [--engine] [--out profiles/mxfp4_dense_gemm_wide.json]
 """
 import argparse
 import gc
@@ -73,6 +80,59 @@ def refit(rows):
     t = torch.tensor([[r["fp8_us"]] for r in rows], dtype=torch.float64)
     sol = torch.linalg.lstsq(a, t).solution.flatten().tolist()
     return dict(w_gbs_per_cu=round(1e-3 / sol[0], 2) if sol[0] > 0 else None, x_gbs_per_cu=round(1e-3 / sol[1], 2) if sol[1] > 0 else None)
+
+
+def bench_mxfp4():
+    dev = torch.device("cuda")
+    rows = []
+    for model, tp, proj, n, k, mode in shapes():
+        if tp != 1:
+            continue
+        w = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
+        wp = ops.pack_weight_tiles(w)
+        w8p = ops.pack_weight_tiles_fp8(w.to(torch.float8_e4m3fn))
+        sc = torch.ones(n // 16, k // 128, device=dev)
+        codes, s4 = ops.quant_pack_mxfp4(w)
+        s4 = ops.tile_scales_mxfp4(s4)
+        del w
+        for m in (1,) + ROWS:
+            x = (torch.randn(m, k, device=dev) * 0.5).to(torch.bfloat16)
+            plans = ops.linear_wide_plan(m, n, k, mode), ops.linear_wide_fp8_plan(m, n, k, mode), ops.linear_wide_mxfp4_plan(m, n, k, mode)
+            ws = [torch.empty(max(p[1], 16), dtype=torch.uint8, device=dev) for p in plans]
+            fns = (lambda out=None: ops.linear_wide(x, wp, mode, out=out, workspace=ws[0], packed=True),
+                   lambda out=None: ops.linear_wide_fp8(x, w8p, sc, mode, out=out, workspace=ws[1]),
+                   lambda out=None: ops.linear_wide_mxfp4(x, codes, s4, mode, out=out, workspace=ws[2]))
+            outs = [fn() for fn in fns]
+            t16, t8, t4 = (layers._time_cold(lambda: fn(out), dev, 5) * 1e3 for fn, out in zip(fns, outs))
+            rows.append(dict(model=model, proj=proj, n=n, k=k, mode=mode, m=m, bf16_us=round(t16, 2), fp8_us=round(t8, 2),
+                             mxfp4_us=round(t4, 2), splits=[p[0] for p in plans], mxfp4_w_gbs=round(n * k * 17 / 32 / t4 / 1e3, 1),
+                             bf16_over_mxfp4=round(t16 / t4, 3), fp8_over_mxfp4=round(t8 / t4, 3)))
+            print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def engine_memory_mxfp4(model="qwen3-32b"):
+    """Resident projection bytes and KV blocks of `model` (dummy weights, eager) with "bf16", "fp8" and "mxfp4_dense"."""
+    from nano_vllm_amd import LLM
+    from nano_vllm_amd.weights import write_synthetic_checkpoint
+    path = tempfile.mkdtemp(prefix=model.replace("-", "_") + "_")
+    write_synthetic_checkpoint(path, model, with_weights=False)
+    out = {}
+    for dt in ("bf16", "fp8", "mxfp4_dense"):
+        llm = LLM(path, dummy_weights=True, max_model_len=4096, enforce_eager=True, weight_dtype=dt)
+        r = llm.model_runner
+        copies = sum(sum(t.numel() * t.element_size() for t in (m.weight_packed, m.weight_fp8_packed, m.weight_scale,
+                                                                 *(m.weight_mxfp4 or ())) if t is not None)
+                     for m in r.model.modules() if isinstance(m, layers.LinearBase))
+        out[dt] = dict(decode_copy_bytes=copies, packed_weight_bytes=r.packed_weight_bytes,
+                       model_bytes_allocated=torch.cuda.memory_allocated() - r._kv_storage.numel() * r._kv_storage.element_size(),
+                       kv_blocks=llm.config.num_kvcache_blocks, kv_block_tokens=r.block_size)
+        llm.exit()
+        del llm, r
+        gc.collect()
+        torch.cuda.empty_cache()
+        print(json.dumps({dt: out[dt]}), flush=True)
+    return out
 
 
 TILE_ROWS = (512, 2048, 8192, 16384)
@@ -184,7 +244,17 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None)
     ap.add_argument("--engine", action="store_true")
     ap.add_argument("--tile", action="store_true")
+    ap.add_argument("--mxfp4", action="store_true")
     args = ap.parse_args()
+    if args.mxfp4:
+        args.out = args.out or "profiles/mxfp4_dense_gemm_wide.json"
+        result = dict(gemm=bench_mxfp4())
+        if args.engine:
+            result["memory_qwen3_32b"] = engine_memory_mxfp4()
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+        sys.exit(0)
     if args.tile:
         args.out = args.out or "profiles/fp8_only_tile_vs_library.json"
         result = dict(tile=bench_tile())
