@@ -261,6 +261,21 @@ int nvl_linear_wide_mxfp4(const void* x, const void* codes, const void* scales_t
                           int mode, void* workspace, size_t workspace_bytes, void* stream);
 int nvl_unpack_mxfp4(const void* codes, const void* scales, void* w_bf16_out, int64_t n, int64_t k, void* stream);
 
+/* W4A16 TILE linear for ANY row count (opt-in: LLM(..., weight_dtype="mxfp4_dense_only"); csrc/gemm_tile_mxfp4.hip): the
+ * same product on the same operands — `codes` is what nvl_quant_pack_mxfp4 writes, `scales_tiled` the tile-major bytes
+ * described above — for the rows nvl_linear_wide_mxfp4's plan refuses (every m > 256: prefill, decode batches of 257-512
+ * sequences), so that the bf16 parameter the library GEMM needed can be released. m >= 1 (partial row tiles are masked;
+ * rows past m of `out` are not written), n % 16 == 0 (mode 1: n % 32 == 0), k % 128 == 0; row offsets are 64-bit. No
+ * workspace, no LDS opt-in, enqueue-only: capturable from the first call.
+ *   mode 0: bf16 [m, n].  mode 1: bf16 [m, n/2] = silu(bf16(gate)) * bf16(up), gate rows first, then up rows
+ *   (nvl_linear_wide mode 1's rounding point).  mode 2: NVL_EUNSUPPORTED (callers that want slabs take mode 0).
+ * The weights enter the matrix instruction as bf16(code x scale): nvl_linear_wide_mxfp4's EXACTNESS contract above holds
+ * here word for word, and nothing beyond it — inside it out = x . W_deq^T with fp32 accumulation, up to the summation order.
+ * Checked on the host before any launch: NVL_EINVAL on null or misaligned (16 bytes) pointers or a mode outside 0 ... 2,
+ * NVL_EUNSUPPORTED ("not covered") for mode 2 and for every shape outside the limits above. */
+int nvl_linear_tile_mxfp4(const void* x, const void* codes, const void* scales_tiled, void* out, int64_t m, int n, int k,
+                          int mode, void* stream);
+
 /* ---- Rotary embedding -----------------------------------------------------
  * Replaces RotaryEmbedding.forward / apply_rotary_emb
  * (layers/rotary_embedding.py:6-14, 37-48): neox (half-split) rotation from a

@@ -32,6 +32,11 @@ Extensions (all optional, behaviour-neutral when unset):
     bf16 parameter is overwritten with the dequantised values, so prefill (library GEMM) and decode compute with the
     same matrix. 4-bit weights are far outside the reference's numerics: opt-in. Refused for qwen3_moe and for
     tensor_parallel_size > 1.
+  * Config.weight_dtype = "mxfp4_dense_only" (dense models, one GPU) quantises exactly as "mxfp4_dense" and then FREES the
+    bf16 projections: rows above 256 (prefill, decode batches of 257-512 sequences) run nvl_linear_tile_mxfp4 on the same
+    codes and scales instead of the library GEMM on a dequantised bf16 copy, so the projections occupy 17/32 byte per
+    weight and the KV pool gets the rest. Same matrix as "mxfp4_dense", another summation order in prefill. Refused for
+    qwen3_moe and for tensor_parallel_size > 1.
 """
 from __future__ import annotations
 
@@ -75,6 +80,7 @@ class Config:
     #                                      "fp8_only": the same, and the bf16 projections are freed (module docstring)
     #                                      "mxfp4": 4-bit expert matrices of a qwen3_moe model (module docstring)
     #                                      "mxfp4_dense": 4-bit decode projections of a dense model (module docstring)
+    #                                      "mxfp4_dense_only": the same, and the bf16 projections are freed (module docstring)
 
     def __post_init__(self):
         assert os.path.isdir(self.model), f"model directory not found: {self.model}"
@@ -86,8 +92,8 @@ class Config:
         self.max_model_len = min(self.max_model_len, self.hf_config.max_position_embeddings)
         assert self.max_num_batched_tokens >= 1 and self.max_num_seqs >= 1
         assert self.kv_cache_dtype in ("bf16", "fp8"), "kv_cache_dtype must be 'bf16' or 'fp8'"
-        assert self.weight_dtype in ("bf16", "fp8", "fp8_only", "mxfp4", "mxfp4_dense"), \
-            "weight_dtype must be 'bf16', 'fp8', 'fp8_only', 'mxfp4' or 'mxfp4_dense'"
+        assert self.weight_dtype in ("bf16", "fp8", "fp8_only", "mxfp4", "mxfp4_dense", "mxfp4_dense_only"), \
+            "weight_dtype must be 'bf16', 'fp8', 'fp8_only', 'mxfp4', 'mxfp4_dense' or 'mxfp4_dense_only'"
         if self.weight_dtype == "fp8_only" and self.tensor_parallel_size > 1:
             raise ValueError("weight_dtype='fp8_only' is single-GPU (the tensor-parallel GEMMs read the bf16 parameter): use 'fp8'")
         if self.weight_dtype == "mxfp4" and getattr(self.hf_config, "model_type", "qwen3") != "qwen3_moe":
@@ -95,6 +101,9 @@ class Config:
                              "(dense models: 'mxfp4_dense' or 'fp8')")
         if self.weight_dtype == "mxfp4_dense" and self.tensor_parallel_size > 1:
             raise ValueError("weight_dtype='mxfp4_dense' is single-GPU for now: use 'fp8' with tensor_parallel_size > 1")
+        if self.weight_dtype == "mxfp4_dense_only" and self.tensor_parallel_size > 1:
+            raise ValueError("weight_dtype='mxfp4_dense_only' is single-GPU (the tensor-parallel GEMMs read the bf16 "
+                             "parameter): use 'fp8' with tensor_parallel_size > 1")
         check_moe_scope(self.hf_config, self.tensor_parallel_size, self.weight_dtype)
 
 

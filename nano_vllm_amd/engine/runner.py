@@ -359,7 +359,8 @@ class ModelRunner:
         keeps its KV pool. weight_dtype="mxfp4" replaces the MoE blocks' expert matrices by their 4-bit form instead, and
         weight_dtype="fp8_only" the dense projections by their e4m3 tiles (half of bf16's bytes, no second copy).
         weight_dtype="mxfp4_dense" keeps the bf16 parameters and budgets the MXFP4 codes + scales (17/32 byte per weight)
-        like the packed copies they replace.
+        like the packed copies they replace; weight_dtype="mxfp4_dense_only" releases the bf16 parameters as "fp8_only"
+        does, so its codes + scales are reported as quantised, not budgeted.
         Returns (bytes packed or quantised, projections left unpacked for lack of budget)."""
         from ..layers import LinearBase, ParallelLMHead
         free, total = torch.cuda.mem_get_info(self.device)
@@ -378,7 +379,7 @@ class ModelRunner:
             if isinstance(m, (LinearBase, ParallelLMHead)):
                 if isinstance(m, LinearBase):      # (lm_head and embedding stay bf16, as in the published FP8 checkpoints)
                     got = m.pack_for_decode(budget - used, weight_dtype=self.config.weight_dtype)
-                    if m.weight_released:          # "fp8_only": quantised in place of the bf16 parameter, as mxfp4
+                    if m.weight_released:          # "fp8_only" / "mxfp4_dense_only": in place of the bf16 parameter, as mxfp4
                         quantised += got           # above — reported, not budgeted (the KV pool is sized from what
                         continue                   # is free after the warm-up's empty_cache())
                 else:

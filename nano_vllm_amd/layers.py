@@ -263,10 +263,10 @@ class LinearBase(nn.Module):
         self.weight_packed: torch.Tensor | None = None     # tile-packed copy for nvl_linear_wide (pack_for_decode)
         self.weight_fp8_packed: torch.Tensor | None = None # e4m3 tile-packed copy + its [N/16, K/128] fp32 scales for
         self.weight_scale: torch.Tensor | None = None      # nvl_linear_wide_fp8 (pack_for_decode(weight_dtype="fp8"))
-        self.weight_mxfp4: tuple | None = None             # (codes, tile-major scales) for nvl_linear_wide_mxfp4
-        #                                                    (pack_for_decode(weight_dtype="mxfp4_dense"))
+        self.weight_mxfp4: tuple | None = None             # (codes, tile-major scales) for nvl_linear_wide_mxfp4 / _tile_mxfp4
+        #                                                    (pack_for_decode(weight_dtype="mxfp4_dense" / "mxfp4_dense_only"))
         self.nk = (output_size, input_size)                # this rank's (n, k): survives the release of `weight`
-        self.weight_released = False                       # weight_dtype="fp8_only": the bf16 storage is gone
+        self.weight_released = False                       # "fp8_only" / "mxfp4_dense_only": the bf16 storage is gone
 
     def _pack_fp8(self, budget_bytes: float) -> int | None:
         """weight_dtype="fp8": quantise this rank's weight as loaded (the merged q|k|v / gate|up matrix) in 128 x 128
@@ -298,13 +298,14 @@ class LinearBase(nn.Module):
         self.weight_scale = scale.repeat_interleave(8, 0)[:n // 16].contiguous()
         return n * k + self.weight_scale.numel() * 4
 
-    def _pack_mxfp4(self, budget_bytes: float) -> int | None:
+    def _pack_mxfp4(self, budget_bytes: float, dequantise_back: bool = True) -> int | None:
         """weight_dtype="mxfp4_dense": quantise this rank's weight as loaded to OCP MXFP4 (ops.quant_pack_mxfp4: e2m1
         codes, one power-of-two scale byte per row and 32 k — per row, so a merged q|k|v / gate|up matrix quantises
         exactly as its parts would), OVERWRITE the bf16 parameter in place with the dequantised values
         (nvl_unpack_mxfp4: code x scale is a bf16 value, so the prefill-sized library GEMM and the decode kernel compute
         with one and the same matrix) and keep the codes + tile-major scales (n k 17/32 bytes) instead of the bf16 packed
-        copy. None: shape not covered by nvl_linear_wide_mxfp4 (the projection keeps today's path)."""
+        copy. None: shape not covered by nvl_linear_wide_mxfp4 (the projection keeps today's path). `dequantise_back` False
+        ("mxfp4_dense_only") leaves the parameter alone: the caller releases it."""
         n, k = self.weight.shape
         if k % 128 or ops.linear_wide_mxfp4_plan(144, n, k, ops.LINEAR_BF16) is None:
             return None
@@ -312,7 +313,8 @@ class LinearBase(nn.Module):
         if nbytes > budget_bytes:
             return -1
         codes, scales = ops.quant_pack_mxfp4(self.weight.data)
-        ops.unpack_mxfp4(codes, scales, out=self.weight.data)
+        if dequantise_back:
+            ops.unpack_mxfp4(codes, scales, out=self.weight.data)
         self.weight_mxfp4 = (codes, ops.tile_scales_mxfp4(scales))
         return nbytes
 
@@ -323,7 +325,9 @@ class LinearBase(nn.Module):
         from it. Returns the extra bytes (0: shape not covered; -1: covered, but the copy does not fit `budget_bytes`
         — ModelRunner._pack_weights). NVL_PACKED_WEIGHTS=0 keeps the row-major weight stream (A/B measurements).
         weight_dtype="fp8_only": as "fp8", then the row-major parameter is RELEASED (`weight.numel() == 0`, `nk` keeps
-        its shape) — every row count runs on the e4m3 tiles (`_released_linear`); returns the bytes of tiles + scales."""
+        its shape) — every row count runs on the e4m3 tiles (`_released_linear`); returns the bytes of tiles + scales.
+        weight_dtype="mxfp4_dense_only": likewise for "mxfp4_dense" — quantised, never dequantised back, released; every
+        row count runs on the codes + tile-major scales; returns their bytes."""
         n, k = self.weight.shape
         if (self.bias is not None or not self.weight.is_cuda or n % 16 or k % 32
                 or os.environ.get("NVL_PACKED_WEIGHTS", "1") == "0"):
@@ -345,6 +349,13 @@ class LinearBase(nn.Module):
                 self.weight.data = torch.empty(0, dtype=self.weight.dtype, device=self.weight.device)
                 self.weight_released = True
                 return got
+        if weight_dtype == "mxfp4_dense_only":
+            # likewise: nvl_linear_tile_mxfp4 serves the row counts the library GEMM read the dequantised parameter for
+            got = self._pack_mxfp4(float("inf"), dequantise_back=False)
+            if got is not None:
+                self.weight.data = torch.empty(0, dtype=self.weight.dtype, device=self.weight.device)
+                self.weight_released = True
+                return got
         skinny = any(ops.linear_decode_splits(144, n, k, mode) for mode in (ops.LINEAR_BF16, ops.LINEAR_PARTIAL))
         wide = (k % 128 == 0 and os.environ.get("NVL_GEMM_WIDE", "auto") != "0"
                 and ops.linear_wide_plan(144, n, k, ops.LINEAR_BF16) is not None)
@@ -360,21 +371,26 @@ class LinearBase(nn.Module):
         return None if self.weight_fp8_packed is None else (self.weight_fp8_packed, self.weight_scale)
 
     def _released_linear(self, x: torch.Tensor, mode: int) -> torch.Tensor:
-        """x . W^T of a projection whose bf16 parameter was released (weight_dtype="fp8_only"): nvl_linear_wide_fp8
-        wherever its plan covers (rows, n, k, mode) — the decode behaviour of "fp8" — and nvl_linear_tile_fp8
-        everywhere else (every row count above 256; a slab request the plan refuses becomes a bf16 output). There is
-        no library GEMM behind this: what neither kernel takes raises NvlError."""
+        """x . W^T of a projection whose bf16 parameter was released (weight_dtype="fp8_only" / "mxfp4_dense_only"): the
+        wide kernel of its format (nvl_linear_wide_fp8 / nvl_linear_wide_mxfp4) wherever its plan covers (rows, n, k, mode)
+        — the decode behaviour of "fp8" / "mxfp4_dense" — and the tile kernel (nvl_linear_tile_fp8 / nvl_linear_tile_mxfp4)
+        everywhere else (every row count above 256; a slab request the plan refuses becomes a bf16 output). There is no
+        library GEMM behind this: what neither kernel takes raises NvlError."""
         n, k = self.nk
+        if self.weight_mxfp4 is not None:
+            kind, w = "mxfp4_dense_only", self.weight_mxfp4
+            wide_plan, wide, tile = ops.linear_wide_mxfp4_plan, ops.linear_wide_mxfp4, ops.linear_tile_mxfp4
+        else:
+            kind, w = "fp8_only", (self.weight_fp8_packed, self.weight_scale)
+            wide_plan, wide, tile = ops.linear_wide_fp8_plan, ops.linear_wide_fp8, ops.linear_tile_fp8
         if not (x.dim() == 2 and x.shape[1] == k and x.dtype == torch.bfloat16 and x.is_cuda):
-            raise ops.NvlError(f"fp8_only projection [{n}, {k}]: input {tuple(x.shape)} {x.dtype} on {x.device} is not covered")
+            raise ops.NvlError(f"{kind} projection [{n}, {k}]: input {tuple(x.shape)} {x.dtype} on {x.device} is not covered")
         x = x.contiguous()
         if x.shape[0] <= DECODE_LINEAR_MAX_ROWS:
-            plan = ops.linear_wide_fp8_plan(x.shape[0], n, k, mode)
+            plan = wide_plan(x.shape[0], n, k, mode)
             if plan is not None:
-                return ops.linear_wide_fp8(x, self.weight_fp8_packed, self.weight_scale, mode,
-                                           workspace=_scratch(plan[1], x.device))
-        return ops.linear_tile_fp8(x, self.weight_fp8_packed, self.weight_scale,
-                                   ops.LINEAR_BF16 if mode == ops.LINEAR_PARTIAL else mode)
+                return wide(x, *w, mode, workspace=_scratch(plan[1], x.device))
+        return tile(x, *w, ops.LINEAR_BF16 if mode == ops.LINEAR_PARTIAL else mode)
 
     def _my_slice(self, loaded: torch.Tensor, dim: int) -> torch.Tensor:
         size = loaded.shape[dim] // self.tp_size
@@ -511,7 +527,8 @@ def decode_linear(x: torch.Tensor, weight: torch.Tensor, mode: int, out: torch.T
     rule: no timing decides), and the rest falls through to the bf16 paths on the dequantised `weight`. `mxfp4`: the
     module's (MXFP4 codes, tile-major scales) — nvl_linear_wide_mxfp4 by the same shape rule."""
     m, k = x.shape
-    n = weight.shape[0] if fp8 is None else fp8[0].shape[0]         # (a released parameter has no shape: "fp8_only")
+    # (a released parameter has no shape: "fp8_only" / "mxfp4_dense_only" take n from their tiles)
+    n = fp8[0].shape[0] if fp8 is not None else mxfp4[0].shape[0] * 16 if mxfp4 is not None else weight.shape[0]
     if mxfp4 is not None:
         plan = ops.linear_wide_mxfp4_plan(m, n, k, mode)
         if plan is not None:
@@ -566,7 +583,8 @@ class MergedColumnParallelLinear(ColumnParallelLinear):
 
     def forward_silu(self, x: torch.Tensor) -> torch.Tensor:
         """SiluAndMul(self(x)) for a gate|up pair; on decode-sized inputs the activation is the GEMM's
-        epilogue (one launch, no [N, 2*inter] round trip) — with weight_dtype="fp8_only" at every row count."""
+        epilogue (one launch, no [N, 2*inter] round trip) — with a released parameter ("fp8_only" / "mxfp4_dense_only") at
+        every row count."""
         if self.weight_released:
             return self._released_linear(x, ops.LINEAR_SILU)
         if (self.bias is None and len(self.output_sizes) == 2 and self.output_sizes[0] == self.output_sizes[1]

@@ -51,6 +51,7 @@ SIGNATURES = {
     "nvl_linear_wide_mxfp4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_size_t,
                                       c_void_p]),
     "nvl_unpack_mxfp4": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "nvl_linear_tile_mxfp4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "nvl_rope_neox": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "nvl_store_kvcache": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64,
                                   c_int, c_void_p]),
@@ -530,6 +531,26 @@ def linear_wide_mxfp4(x: torch.Tensor, codes: torch.Tensor, scales_tiled: torch.
     assert not ws_bytes or workspace.numel() * workspace.element_size() >= ws_bytes
     _check(lib().nvl_linear_wide_mxfp4(x.data_ptr(), codes.data_ptr(), scales_tiled.data_ptr(), out.data_ptr(), m, n, k, mode,
                                        workspace.data_ptr() if ws_bytes else None, ws_bytes, _stream()))
+    return out
+
+
+def linear_tile_mxfp4(x: torch.Tensor, codes: torch.Tensor, scales_tiled: torch.Tensor, mode: int = LINEAR_BF16,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """x [M, K] bf16 . W_deq^T over MXFP4 weights for ANY M (nvl_linear_tile_mxfp4): operands as linear_wide_mxfp4. mode
+    LINEAR_BF16 -> bf16 [M, N], LINEAR_SILU -> bf16 [M, N/2]; LINEAR_PARTIAL is not offered. `out` may have more than M
+    rows: the rows past M are left untouched."""
+    _dev(x, "x")
+    assert x.dim() == 2 and x.is_contiguous() and codes.is_contiguous() and scales_tiled.is_contiguous()
+    assert x.dtype == torch.bfloat16 and codes.dtype == torch.uint8 and scales_tiled.dtype == torch.uint8
+    m, k = x.shape
+    n = codes.shape[0] * 16
+    assert tuple(codes.shape) == (n // 16, k // 128, 64, 16) and tuple(scales_tiled.shape) == (n // 16, k // 128, 16, 4)
+    cols = n // 2 if mode == LINEAR_SILU else n
+    if out is None:
+        out = torch.empty((m, cols), dtype=torch.bfloat16, device=x.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape[0] >= m and out.shape[1] == cols
+    _check(lib().nvl_linear_tile_mxfp4(x.data_ptr(), codes.data_ptr(), scales_tiled.data_ptr(), out.data_ptr(), m, n, k, mode,
+                                       _stream()))
     return out
 
 

@@ -21,6 +21,14 @@ MALL before every sample, best of 5. With --engine it adds resident projection b
 weights with "bf16", "fp8" and "mxfp4_dense".
 
     python tools/gemm_fp8_bench.py --mxfp4 [--engine] [--out profiles/mxfp4_dense_gemm_wide.json]
+
+--mxfp4 --tile: nvl_linear_tile_mxfp4 (weight_dtype="mxfp4_dense_only") on every full-width Qwen3-8B / 32B projection in the
+mode prefill uses, at 512 / 2048 / 8192 / 16384 rows against F.linear on the dequantised bf16 weight (plus the silu_mul
+launch for gate|up) and against nvl_linear_tile_fp8, and at 144 / 200 / 256 rows against nvl_linear_wide_mxfp4. Cold L2 /
+MALL before every sample, best of 5, device events. With --engine it adds "mxfp4_dense" against "mxfp4_dense_only": tok/s
+on qwen3-8b (256 sequences), and resident bytes + KV blocks of qwen3-32b dummy weights.
+
+    python tools/gemm_fp8_bench.py --mxfp4 --tile [--engine] [--out profiles/mxfp4_dense_only_tile.json]
 """
 import argparse
 import gc
@@ -111,14 +119,59 @@ def bench_mxfp4():
     return rows
 
 
-def engine_memory_mxfp4(model="qwen3-32b"):
-    """Resident projection bytes and KV blocks of `model` (dummy weights, eager) with "bf16", "fp8" and "mxfp4_dense"."""
+def bench_tile_mxfp4():
+    import torch.nn.functional as F
+    dev = torch.device("cuda")
+    tile, wide = [], []
+    for model, tp, proj, n, k, _ in shapes():
+        if tp != 1:
+            continue
+        mode = ops.LINEAR_SILU if proj == "gate_up" else ops.LINEAR_BF16          # (no slabs at these row counts)
+        wd = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
+        codes, s4 = ops.quant_pack_mxfp4(wd)
+        ops.unpack_mxfp4(codes, s4, out=wd)                                       # the matrix "mxfp4_dense" multiplies in prefill
+        s4 = ops.tile_scales_mxfp4(s4)
+        w8p = ops.pack_weight_tiles_fp8((torch.randn(n, k, device=dev) * 0.05).to(torch.float8_e4m3fn))
+        sc = torch.exp2(torch.randint(-8, -3, (n // 16, k // 128), device=dev).float())
+        for m in TILE_ROWS:
+            x = (torch.randn(m, k, device=dev) * 0.5).to(torch.bfloat16)
+            out = ops.linear_tile_mxfp4(x, codes, s4, mode)
+            lib = (lambda: ops.silu_mul(F.linear(x, wd))) if mode == ops.LINEAR_SILU else (lambda: F.linear(x, wd))
+            same = float((out.float() - lib().float()).abs().max()) / float(out.float().abs().max())
+            ops.linear_tile_fp8(x, w8p, sc, mode, out=out)                        # (warm-up of the third path)
+            t4, tl, t8 = (layers._time_cold(fn, dev, 5) * 1e3 for fn in (
+                lambda: ops.linear_tile_mxfp4(x, codes, s4, mode, out=out), lib, lambda: ops.linear_tile_fp8(x, w8p, sc, mode, out=out)))
+            tile.append(dict(model=model, proj=proj, n=n, k=k, mode=mode, m=m, tile_mxfp4_us=round(t4, 1), library_us=round(tl, 1),
+                             tile_fp8_us=round(t8, 1), tile_mxfp4_pflops=round(2.0 * m * n * k / t4 / 1e9, 3),
+                             library_over_tile_mxfp4=round(tl / t4, 3), tile_fp8_over_tile_mxfp4=round(t8 / t4, 3),
+                             max_rel_diff=round(same, 5)))
+            print(json.dumps(tile[-1]), flush=True)
+            del x, out
+        for m in (144, 200, 256):
+            x = (torch.randn(m, k, device=dev) * 0.5).to(torch.bfloat16)
+            plan = ops.linear_wide_mxfp4_plan(m, n, k, mode)
+            if plan is None:
+                continue
+            ws = torch.empty(max(plan[1], 16), dtype=torch.uint8, device=dev)
+            out = ops.linear_wide_mxfp4(x, codes, s4, mode, workspace=ws)
+            ops.linear_tile_mxfp4(x, codes, s4, mode, out=out)
+            tw, tt = (layers._time_cold(fn, dev, 5) * 1e3 for fn in (
+                lambda: ops.linear_wide_mxfp4(x, codes, s4, mode, out=out, workspace=ws), lambda: ops.linear_tile_mxfp4(x, codes, s4, mode, out=out)))
+            wide.append(dict(model=model, proj=proj, n=n, k=k, mode=mode, m=m, wide_mxfp4_us=round(tw, 1), tile_mxfp4_us=round(tt, 1),
+                             wide_over_tile=round(tw / tt, 3)))
+            print(json.dumps(wide[-1]), flush=True)
+        del wd, codes, s4, w8p, sc
+    return tile, wide
+
+
+def engine_memory_mxfp4(model="qwen3-32b", dtypes=("bf16", "fp8", "mxfp4_dense")):
+    """Resident projection bytes and KV blocks of `model` (dummy weights, eager) with each of `dtypes`."""
     from nano_vllm_amd import LLM
     from nano_vllm_amd.weights import write_synthetic_checkpoint
     path = tempfile.mkdtemp(prefix=model.replace("-", "_") + "_")
     write_synthetic_checkpoint(path, model, with_weights=False)
     out = {}
-    for dt in ("bf16", "fp8", "mxfp4_dense"):
+    for dt in dtypes:
         llm = LLM(path, dummy_weights=True, max_model_len=4096, enforce_eager=True, weight_dtype=dt)
         r = llm.model_runner
         copies = sum(sum(t.numel() * t.element_size() for t in (m.weight_packed, m.weight_fp8_packed, m.weight_scale,
@@ -246,6 +299,17 @@ if __name__ == "__main__":
     ap.add_argument("--tile", action="store_true")
     ap.add_argument("--mxfp4", action="store_true")
     args = ap.parse_args()
+    if args.mxfp4 and args.tile:
+        args.out = args.out or "profiles/mxfp4_dense_only_tile.json"
+        tile, wide = bench_tile_mxfp4()
+        result = dict(tile=tile, tile_vs_wide=wide)
+        if args.engine:
+            result["engine_qwen3_8b_256seq"] = bench_engine(("mxfp4_dense", "mxfp4_dense_only"))
+            result["memory_qwen3_32b"] = engine_memory_mxfp4(dtypes=("mxfp4_dense", "mxfp4_dense_only"))
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+        sys.exit(0)
     if args.mxfp4:
         args.out = args.out or "profiles/mxfp4_dense_gemm_wide.json"
         result = dict(gemm=bench_mxfp4())
