@@ -526,6 +526,50 @@ int nvl_sample_merge(const void* best_packed, int parts, int64_t part_stride_byt
 int nvl_feed_tokens(int64_t* ids, const int32_t* src_row, const int64_t* prev_tokens,
                     int64_t n, void* stream);
 
+/* ---- Sampling penalties (presence / frequency / repetition) ---------------------------------
+ * The token history lives on the device, in a TOKEN CACHE that shadows the paged KV cache:
+ * token_cache is int32 [cache_slots], cache_slots = num_blocks * block_size, and entry `slot`
+ * holds the id of the token whose K/V sit at KV slot `slot`. A sequence's history is therefore
+ * its block table; prefix-cache hits, preemption and eviction need no action of their own.
+ *   nvl_store_tokens      : token_cache[slots[i]] = (int32) ids[i] wherever 0 <= slots[i] <
+ *                           cache_slots (prefill steps: the step's staged ids and slot mapping).
+ *   nvl_feed_store_tokens : nvl_feed_tokens' copy AND that store in one launch (first node of a
+ *                           decode step): id = src_row[i] >= 0 ? prev_tokens[src_row[i]] : ids[i];
+ *                           ids[i] = id; token_cache[slots[i]] = id under the same slot test.
+ *                           `ids` ends up exactly as nvl_feed_tokens leaves it.
+ *   nvl_apply_penalties   : in place on logits bf16 [batch, vocab] (row stride given), BEFORE
+ *                           temperature, top-k / top-p and the race. Row b's tokens are
+ *                           token_cache[bt[b][p / block_size] * block_size + p % block_size] for
+ *                           p < context_lens[b]; c(t) counts t among the positions
+ *                           p >= prompt_lens[b]; for every token t of the list, in fp32 with no
+ *                           contraction and ONE rounding to bf16 (nearest even) at the end:
+ *                               x = l_t;  x = x > 0 ? x / repetition[b] : x * repetition[b];
+ *                               x = x - frequency[b] * c(t);  x = x - (c(t) > 0 ? presence[b] : 0)
+ *                           Columns of tokens that are not in the list keep their bits; a row with
+ *                           presence == 0, frequency == 0, repetition == 1, or context_lens[b] == 0
+ *                           (graph padding), is not touched. block_tables: int32 [batch, max_blocks]
+ *                           with row stride bt_stride; entries < 0, slots >= cache_slots and ids
+ *                           outside [0, vocab) are skipped, never dereferenced.
+ *                           One workgroup per row and 77,824 columns; counts are integers in an LDS
+ *                           table over those columns and each listed column is written once, from final counts:
+ *                           bit-identical run to run. Bounds, checked on the host (NVL_EINVAL):
+ *                           vocab <= 155,648; block_size a power of two; max_context <= 16,383
+ *                           (a count is a 14-bit field, and a row's token list is held in 16
+ *                           registers of 1,024 lanes) - longer contexts are refused, never saturated.
+ * All three are enqueue-only, use no workspace and are hipGraph-capturable; the first call of
+ * the penalty entry on a device opts its kernel into 152 KiB of LDS and must precede any capture. */
+int nvl_store_tokens(const int64_t* ids, const int32_t* slots, int32_t* token_cache,
+                     int64_t cache_slots, int64_t n, void* stream);
+int nvl_feed_store_tokens(int64_t* ids, const int32_t* src_row, const int64_t* prev_tokens,
+                          const int32_t* slots, int32_t* token_cache, int64_t cache_slots,
+                          int64_t n, void* stream);
+int nvl_apply_penalties(void* logits, int64_t logits_row_stride, const int32_t* token_cache,
+                        int64_t cache_slots, const int32_t* block_tables, int64_t bt_stride,
+                        int max_blocks, const int32_t* context_lens, const int32_t* prompt_lens,
+                        const float* presence, const float* frequency, const float* repetition,
+                        int64_t batch, int64_t vocab, int block_size, int64_t max_context,
+                        void* stream);
+
 /* ---- Tensor-parallel collectives over xGMI (decode-sized messages) -----------------------
  * Replace dist.all_reduce after the row-parallel GEMMs (layers/linear.py:153-156) and after
  * the vocab-parallel embedding (layers/embed_head.py:41), and dist.gather of the logits

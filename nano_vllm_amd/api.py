@@ -8,6 +8,10 @@ Extensions (all optional, behaviour-neutral when unset):
   * SamplingParams.top_k / top_p truncate the distribution before the draw (top-k first, then top-p renormalised over
     the survivors, ties at a cut kept); 0 / -1 and 1.0 switch them off. Single GPU only: tensor_parallel_size > 1
     refuses such a request.
+  * SamplingParams.presence_penalty / frequency_penalty / repetition_penalty change a row's raw logits before temperature
+    and top-k / top-p, with the usual semantics: l / r or l * r (by sign) for every token of the prompt or the output,
+    then - frequency x (count in the output) - presence x (count > 0). 0 / 0 / 1 switch them off. The token history is
+    read on the device (nvl_apply_penalties). Single GPU only, and max_model_len <= 16,383: other requests are refused.
   * Config.seed seeds the counter-based sampler RNG.
   * Config.dummy_weights = True initialises random weights on device instead of reading
     *.safetensors (no 8B/32B checkpoints exist offline).
@@ -44,6 +48,9 @@ import os
 from dataclasses import dataclass
 
 
+PENALTY_MAX_CONTEXT = 16383       # nvl_apply_penalties: a 14-bit count per token, 16 positions per lane (include/nvl.h)
+
+
 @dataclass(slots=True)
 class SamplingParams:
     temperature: float = 1.0
@@ -51,8 +58,16 @@ class SamplingParams:
     ignore_eos: bool = False
     top_k: int = 0                # 0 or -1: off
     top_p: float = 1.0            # 1.0: off
+    presence_penalty: float = 0.0     # 0.0: off
+    frequency_penalty: float = 0.0    # 0.0: off
+    repetition_penalty: float = 1.0   # 1.0: off
+
+    @property
+    def penalised(self) -> bool:
+        return self.presence_penalty != 0 or self.frequency_penalty != 0 or self.repetition_penalty != 1
 
     def __post_init__(self):
+        assert self.repetition_penalty > 0, "repetition_penalty must be > 0 (1.0: off)"
         assert self.temperature == 0 or self.temperature > 1e-10, "temperature must be 0 (greedy) or > 1e-10"
         assert self.max_tokens >= 1
         assert self.top_k >= -1, "top_k must be >= -1 (0 or -1: off)"

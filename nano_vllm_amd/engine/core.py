@@ -12,7 +12,7 @@ import os
 from dataclasses import fields
 from time import perf_counter
 
-from ..api import Config, SamplingParams
+from ..api import PENALTY_MAX_CONTEXT, Config, SamplingParams
 from .sched import Scheduler
 from .seq import Sequence
 
@@ -110,6 +110,17 @@ class LLMEngine:
         if self.config.tensor_parallel_size > 1 and (sampling_params.top_k > 0 or sampling_params.top_p < 1):
             raise ValueError("top_k / top_p are not supported with tensor_parallel_size > 1 (the vocabulary is sharded "
                              "across the ranks): run the request without them or on a single GPU")
+        # the penalty kernel sits between lm_head and the sampler and needs the whole row too; its per-token count is
+        # a 14-bit field, so the longest context the engine can reach must fit it
+        if sampling_params.penalised:
+            if self.config.tensor_parallel_size > 1:
+                raise ValueError("presence_penalty / frequency_penalty / repetition_penalty are not supported with "
+                                 "tensor_parallel_size > 1 (the vocabulary is sharded across the ranks): run the request "
+                                 "without them or on a single GPU")
+            if self.config.max_model_len > PENALTY_MAX_CONTEXT:
+                raise ValueError(f"presence_penalty / frequency_penalty / repetition_penalty need max_model_len <= "
+                                 f"{PENALTY_MAX_CONTEXT} (the penalty kernel's context bound), this engine has "
+                                 f"{self.config.max_model_len}: lower max_model_len or run the request without them")
         return prompt
 
     def _new_sequence(self, prompt: list[int], sampling_params: SamplingParams) -> Sequence:

@@ -34,7 +34,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
-from ..api import Config, model_geometry
+from ..api import PENALTY_MAX_CONTEXT, Config, model_geometry
 from ..attn_meta import get_context, reset_context, set_context
 from ..layers import Sampler
 from ..qwen3 import Qwen3ForCausalLM, Qwen3MoeForCausalLM, Qwen3MoeSparseBlock
@@ -465,12 +465,14 @@ class ModelRunner:
             ("ids", np.int64, (mb,)), ("pos", np.int64, (mb,)), ("rng", np.uint64, (2,)), ("rkey", np.int64, (mb,)),
             ("slots", np.int32, (mb,)), ("ctx", np.int32, (mb,)), ("temps", np.float32, (mb,)),
             ("topk", np.int32, (mb,)), ("topp", np.float32, (mb,)), ("src", np.int32, (mb,)), ("shp", np.int32, (1 + mb,)), ("bt", np.int32, (mb, w)),
+            ("ppen", np.float32, (mb,)), ("fpen", np.float32, (mb,)), ("rpen", np.float32, (mb,)), ("plen", np.int32, (mb,)),
         ], self.device, host_copies=2)
         for image in self.dstage.nps:
             image["slots"][:] = -1
             image["bt"][:] = -1
             image["src"][:] = -1
             image["topp"][:] = 1.0
+            image["rpen"][:] = 1.0
         self.dstage.upload()
         # per pinned image: (seq id, #blocks, allocation stamp) per decode row whose block-table row is current
         self._row_keys = [np.full((mb, 3), -1, dtype=np.int64) for _ in self.dstage.nps]
@@ -482,7 +484,10 @@ class ModelRunner:
             ("slots", np.int32, (nt,)), ("cu_q", np.int32, (ns + 1,)), ("cu_k", np.int32, (ns + 1,)),
             ("temps", np.float32, (ns,)), ("topk", np.int32, (ns,)), ("topp", np.float32, (ns,)),
             ("bt", np.int32, (ns, w)),
+            ("ppen", np.float32, (ns,)), ("fpen", np.float32, (ns,)), ("rpen", np.float32, (ns,)), ("plen", np.int32, (ns,)),
+            ("ctx", np.int32, (ns,)),
         ], self.device)
+        self.pstage.np["rpen"][:] = 1.0
         self.step_count = 0
         self.share_prefix = False            # (decided below, once the device side exists)
         self._seen_cached_kv = False         # has any prefill step attended to K/V it did not compute itself?
@@ -521,11 +526,14 @@ class ModelRunner:
                                                                       self.block_size))
         self.share_prefix_min_bytes = float(os.environ.get("NVL_SHARED_PREFIX_MIN_MB", "100")) * 1e6
         self.decode_plan_px = torch.zeros(ops.decode_plan_bytes(), dtype=torch.uint8, device=self.device)
-        self.graphs_px: dict[tuple, torch.cuda.CUDAGraph] = {}      # (bucket, group slots, filtered) -> variant graph
+        self.graphs_px: dict[tuple, torch.cuda.CUDAGraph] = {}      # (bucket, group slots, filtered, penalised) -> variant graph
         self.prefix_steps = 0                # decode steps that ran the shared-prefix pass (reporting)
         self.prefix_multi_steps = 0          # ... with more than one shared prefix in the batch
         self.filtered_steps = 0              # decode steps sampled by the top-k / top-p kernel (some row had a filter on)
         self.filtered_graph_steps = 0        # ... that were a graph replay
+        self.penalised_steps = 0             # decode steps with the penalty kernel before the sampler (some row had a penalty on)
+        self.penalised_graph_steps = 0       # ... that were a graph replay
+        self.token_cache = None              # int32 [num_blocks * block_size], allocated with the KV pool
         self._step_done = [torch.cuda.Event(), torch.cuda.Event()]
         # TP with the xGMI P2P collectives: every spin of those kernels is bounded, and a timeout is LATCHED in the shared
         # flag region while the step carries on with an invalid sum. The last node of every step (prefill and decode,
@@ -580,6 +588,9 @@ class ModelRunner:
         if fp8:
             self._kv_storage = self._kv_storage.view(torch.float8_e4m3fn)      # zero bytes are +0.0 in e4m3 too
         self.kv_cache = self._kv_storage.transpose(0, 1)
+        # the token cache shadows the pool slot for slot (entry = id of the token whose K/V sit there): 4 bytes per slot,
+        # out of the headroom gpu_memory_utilization leaves — the block count above is the formula's, unchanged
+        self.token_cache = torch.zeros(cfg.num_kvcache_blocks * self.block_size, dtype=torch.int32, device=self.device)
         layer = 0
         for module in self.model.modules():
             if hasattr(module, "k_cache") and hasattr(module, "v_cache"):
@@ -599,6 +610,7 @@ class ModelRunner:
         cu_q[0] = cu_k[0] = 0
         max_q = max_k = 0
         have_slots = True
+        pen = False
         for i, seq in enumerate(seqs):
             start = seq.num_cached_tokens
             lq = seq.num_scheduled_tokens
@@ -616,18 +628,22 @@ class ModelRunner:
                 have_slots = False
             st["temps"][i] = seq.temperature
             st["topk"][i], st["topp"][i] = seq.top_k, seq.top_p
+            st["ppen"][i], st["fpen"][i], st["rpen"][i] = seq.presence_penalty, seq.frequency_penalty, seq.repetition_penalty
+            st["plen"][i], st["ctx"][i] = seq.num_prompt_tokens, end
             st["rkey"][i] = seq.rng_key | (end << 32)          # the draw of the token that will sit at position `end`
             n += lq
         ns = len(seqs)
         paged = int(cu_k[ns]) > int(cu_q[ns])                  # some K/V must come from the cache
+        pen = have_slots and self._penalised(st, ns)           # the penalty kernel reads the rows' history through `bt`
         if paged:
             self._seen_cached_kv = True                        # (prefix-cache hits or chunked prefill: blocks MAY be shared)
+        if paged or pen:
             bt = st["bt"]
             for i, seq in enumerate(seqs):
                 t = seq.block_table
                 bt[i, :len(t)] = t
                 bt[i, len(t):] = -1
-        return dict(n=n, ns=ns, max_q=max_q, max_k=max_k, paged=paged, have_slots=have_slots)
+        return dict(n=n, ns=ns, max_q=max_q, max_k=max_k, paged=paged, have_slots=have_slots, pen=pen)
 
     def prepare_decode(self, seqs: list[Sequence], prev_rows: dict | None = None) -> int:
         """Fill the current pinned decode image (semantics of model_runner.py:172-188); returns bs.
@@ -656,6 +672,10 @@ class ModelRunner:
         st["temps"][:n] = [s.temperature for s in seqs]
         st["topk"][:n] = [s.top_k for s in seqs]
         st["topp"][:n] = [s.top_p for s in seqs]
+        st["ppen"][:n] = [s.presence_penalty for s in seqs]
+        st["fpen"][:n] = [s.frequency_penalty for s in seqs]
+        st["rpen"][:n] = [s.repetition_penalty for s in seqs]
+        st["plen"][:n] = [s.num_prompt_tokens for s in seqs]
         # block tables: rewrite a row only when its (sequence, #blocks, allocation stamp) changed in THIS image.
         # The stamp matters: a preempted sequence that is prefilled again may come back to the same row with the
         # same number of blocks but other block ids (kv_blocks.BlockManager.allocate).
@@ -715,24 +735,37 @@ class ModelRunner:
         """Does any of the first n staged rows have a top-k / top-p filter on? (Every rank reads the same image.)"""
         return bool((image["topk"][:n] > 0).any() or (image["topp"][:n] < 1).any())
 
-    def _sample(self, hidden, temps, out, rng, sampler, rkey=None, filters=None):
+    @staticmethod
+    def _penalised(image: dict, n: int) -> bool:
+        """Does any of the first n staged rows have a presence / frequency / repetition penalty on?"""
+        return bool((image["ppen"][:n] != 0).any() or (image["fpen"][:n] != 0).any() or (image["rpen"][:n] != 1).any())
+
+    def _sample(self, hidden, temps, out, rng, sampler, rkey=None, filters=None, penalties=None):
         """lm_head + sampler on the current stream; TP > 1: every rank samples its vocabulary shard and the
         per-row winners are merged on every rank (no [B, V] gather, embed_head.py:62-65). `filters`: the step's
-        (top_k, top_p) rows when some row has a filter on — the top-k / top-p kernel samples the whole step."""
+        (top_k, top_p) rows when some row has a filter on — the top-k / top-p kernel samples the whole step.
+        `penalties`: the step's (block tables, context lengths, prompt lengths, presence, frequency, repetition) rows
+        when some row has a penalty on — nvl_apply_penalties rewrites the logits before either sampler reads them."""
         col0 = self.rank * self.geo["vocab_per_rank"]
         if self.world_size == 1:
             top_k, top_p = filters if filters is not None else (None, None)
-            sampler(self.model.compute_logits(hidden), temps, out=out, offset_dev=rng, row_keys=rkey, top_k=top_k, top_p=top_p)
+            logits = self.model.compute_logits(hidden)
+            if penalties is not None:
+                ops.apply_penalties(logits, self.token_cache, *penalties, self.block_size, self.config.max_model_len)
+            sampler(logits, temps, out=out, offset_dev=rng, row_keys=rkey, top_k=top_k, top_p=top_p)
         else:
             assert filters is None, "top-k / top-p needs the whole vocabulary row: requests with a filter are refused at TP > 1"
+            assert penalties is None, "the penalties need the whole vocabulary row: such requests are refused at TP > 1"
             logits = self.model.compute_logits_shard(hidden)
             sampler.forward_shard(logits, temps, col0, out, offset_dev=rng, row_keys=rkey)
 
-    def _decode_rows(self, r0: int, r1: int, ws, sampler, plan=None, prefix: int = 0, filtered: bool = False):
+    def _decode_rows(self, r0: int, r1: int, ws, sampler, plan=None, prefix: int = 0, filtered: bool = False,
+                     penalised: bool = False):
         """Decode forward for rows [r0, r1) of the static device buffers, on the current stream. `prefix` > 0: the plan
         carries the step's shared-prefix groups (staged as `shp`), the attention launches run the shared pass with that
         many group slots per pack (1: one shared prefix in the step; MAX_PREFIX_GROUPS: several). `filtered`: the sampler
-        node is the top-k / top-p kernel, reading the rows' staged filters."""
+        node is the top-k / top-p kernel, reading the rows' staged filters. `penalised`: the penalty kernel runs on the
+        logits before the sampler node, reading the rows' staged penalties and their history in the token cache."""
         t = self.dstage.t
         assert not prefix or r0 == 0           # (the member flags are staged per row of the whole batch)
         if plan is not None:
@@ -744,7 +777,9 @@ class ModelRunner:
                     decode_plan=plan, shared_prefix=bool(prefix) and plan is not None)
         hidden = self.model(t["ids"][r0:r1], t["pos"][r0:r1])
         self._sample(hidden, t["temps"][r0:r1], self.tokens_dev[r0:r1], t["rng"][:1], sampler, t["rkey"][r0:r1],
-                     (t["topk"][r0:r1], t["topp"][r0:r1]) if filtered else None)
+                     (t["topk"][r0:r1], t["topp"][r0:r1]) if filtered else None,
+                     (t["bt"][r0:r1], t["ctx"][r0:r1], t["plen"][r0:r1], t["ppen"][r0:r1], t["fpen"][r0:r1],
+                      t["rpen"][r0:r1]) if penalised else None)
         reset_context()
         self._collect_comm_status()
 
@@ -761,17 +796,18 @@ class ModelRunner:
                                "collectives over the process group instead")
 
     @torch.inference_mode()
-    def _forward_decode(self, bs: int, prefix: int = 0, filtered: bool = False):
+    def _forward_decode(self, bs: int, prefix: int = 0, filtered: bool = False, penalised: bool = False):
         """Decode forward on the static device buffers (captured per bucket, or run eagerly): layers + lm_head
         + sampler, at any TP degree (the reference captures the layers only and runs lm_head, the logits
         gather and the sampler eagerly, model_runner.py:212,218). (A micro-batched form — two half-batch chains on
         two branches of the captured graph — was measured slower in rounds 1-3 and is gone: DESIGN.md, measured
         negatives.)"""
-        # input ids of sequences that were in the previous decode step come straight from its sampled ids
+        # input ids of sequences that were in the previous decode step come straight from its sampled ids; the same node
+        # writes every row's input id — the token at position len - 1 — into the token cache at that position's slot
         t = self.dstage.t
-        ops.feed_tokens(t["ids"][:bs], t["src"][:bs], self.tokens_dev)
+        ops.feed_store_tokens(t["ids"][:bs], t["src"][:bs], self.tokens_dev, t["slots"][:bs], self.token_cache)
         plan = (self.decode_plan_px if prefix else self.decode_plan) if self.use_plan else None
-        self._decode_rows(0, bs, self.decode_ws, self.sampler, plan, prefix, filtered)
+        self._decode_rows(0, bs, self.decode_ws, self.sampler, plan, prefix, filtered, penalised)
 
     @torch.inference_mode()
     def _launch_decode(self, n: int) -> None:
@@ -787,23 +823,27 @@ class ModelRunner:
         # a step with a top-k / top-p filter in any row swaps the sampler node; every other step launches what it always did
         filtered = self._filtered(self.dstage.np, n)
         self.filtered_steps += int(filtered)
-        key = (bucket, prefix, filtered)
+        # ... and one with a penalty in any row gets the penalty kernel in front of it
+        penalised = self._penalised(self.dstage.np, n)
+        self.penalised_steps += int(penalised)
+        key = (bucket, prefix, filtered, penalised)
         if bucket is not None and prefix and key not in self.graphs_px and not self._capture_variant_graph(*key):
             # the capture failed (single rank only; _capture_variant_graph raises under TP): this step runs without the
             # pass, on a plan built without the staged groups
             self.prefix_steps -= 1
             self.prefix_multi_steps -= int(prefix > 1)
             prefix = 0
-            key = (bucket, 0, filtered)
-        if bucket is not None and filtered and key not in self.graphs_px and not self._capture_variant_graph(*key):
-            bucket = None                    # no graph with the filtering sampler for this bucket: the step runs eagerly
-        if bucket is not None and (prefix or filtered):
+            key = (bucket, 0, filtered, penalised)
+        if bucket is not None and (filtered or penalised) and key not in self.graphs_px and not self._capture_variant_graph(*key):
+            bucket = None                    # no graph with these sampling nodes for this bucket: the step runs eagerly
+        if bucket is not None and (prefix or filtered or penalised):
             self.graphs_px[key].replay()
             self.filtered_graph_steps += int(filtered)
+            self.penalised_graph_steps += int(penalised)
         elif bucket is not None:
             self.graphs[bucket].replay()
         else:
-            self._forward_decode(n, prefix, filtered)
+            self._forward_decode(n, prefix, filtered, penalised)
         host = self.tokens_host if self._flight_parity == 0 else self.tokens_host_b
         done = self._step_done[self._flight_parity]
         if self.rank == 0:
@@ -854,11 +894,17 @@ class ModelRunner:
         self.pstage.upload()
         t = self.pstage.t
         n, ns = info["n"], info["ns"]
+        if info["have_slots"]:                                 # ALWAYS: a later, penalised request may hit these blocks
+            ops.store_tokens(t["ids"][:n], t["slots"][:n], self.token_cache)
         set_context(True, t["cu_q"][:ns + 1], t["cu_k"][:ns + 1], info["max_q"], info["max_k"],
                     t["slots"][:n] if info["have_slots"] else None, None, t["bt"][:ns] if info["paged"] else None)
         hidden = self.model(t["ids"][:n], t["pos"][:n])
         filters = (t["topk"][:ns], t["topp"][:ns]) if self._filtered(self.pstage.np, ns) else None
-        self._sample(hidden, t["temps"][:ns], self.tokens_dev[:ns], t["rng"][:1], self.sampler, t["rkey"][:ns], filters)
+        # a penalised row's first token gets its penalties too (repetition over the prompt): context = the row's `end`
+        penalties = (t["bt"][:ns], t["ctx"][:ns], t["plen"][:ns], t["ppen"][:ns], t["fpen"][:ns],
+                     t["rpen"][:ns]) if info.get("pen") else None
+        self._sample(hidden, t["temps"][:ns], self.tokens_dev[:ns], t["rng"][:1], self.sampler, t["rkey"][:ns], filters,
+                     penalties)
         reset_context()
         self._collect_comm_status()
 
@@ -917,14 +963,19 @@ class ModelRunner:
             t = self.dstage.t
             ops.sample_topk_topp(torch.zeros(1, 8, dtype=torch.bfloat16, device=self.device), t["temps"][:1],
                                  t["topk"][:1], t["topp"][:1], 0, 0, out=self.tokens_dev[:1])
+            # ... and of the penalty kernel (its LDS opt-in is made by the first call; row 0 is padding: nothing is done)
+            ops.apply_penalties(torch.zeros(1, 8, dtype=torch.bfloat16, device=self.device), self.token_cache,
+                                t["bt"][:1], t["ctx"][:1], t["plen"][:1], t["ppen"][:1], t["fpen"][:1], t["rpen"][:1],
+                                self.block_size, min(self.config.max_model_len, PENALTY_MAX_CONTEXT))
         torch.cuda.synchronize()
         from .. import layers
         layers.release_tuning_scratch()                 # the decode-GEMM choices of every bucket are made by now
 
     @torch.inference_mode()
-    def _capture_variant_graph(self, bs: int, groups: int = 0, filtered: bool = False) -> bool:
+    def _capture_variant_graph(self, bs: int, groups: int = 0, filtered: bool = False, penalised: bool = False) -> bool:
         """A second decode graph of bucket `bs`: WITH the shared-prefix attention pass (`groups` > 0 group slots) and / or
-        with the top-k / top-p kernel as its sampler node (`filtered`), captured the first time a step wants
+        with the top-k / top-p kernel as its sampler node (`filtered`) and / or the penalty kernel in front of the
+        sampler node (`penalised`), captured the first time a step wants
         it (most workloads never do; the largest bucket's prefix graph is captured at start-up). No warm-up run on the serving path:
         the static buffers hold a real step's inputs by now, every choice the launches make was made when the bucket's
         plain graph was captured, and the allocations come out of the plain graphs' pool. Every rank captures at the same
@@ -935,7 +986,7 @@ class ModelRunner:
         graph = torch.cuda.CUDAGraph()
         try:
             with torch.cuda.graph(graph, self.graph_pool):
-                self._forward_decode(bs, prefix=groups, filtered=filtered)
+                self._forward_decode(bs, prefix=groups, filtered=filtered, penalised=penalised)
         except Exception as e:      # OOM of the pool's headroom, a launch refused inside the capture
             if self.world_size > 1:
                 raise
@@ -944,7 +995,7 @@ class ModelRunner:
                 warnings.warn(f"shared-prefix graph of bucket {bs} could not be captured ({e!r}); the pass is off")
                 self.share_prefix = False
             else:
-                warnings.warn(f"top-k / top-p graph of bucket {bs} could not be captured ({e!r}); the step runs eagerly")
+                warnings.warn(f"top-k / top-p / penalty graph of bucket {bs} could not be captured ({e!r}); the step runs eagerly")
             return False
-        self.graphs_px[(bs, groups, filtered)] = graph
+        self.graphs_px[(bs, groups, filtered, penalised)] = graph
         return True

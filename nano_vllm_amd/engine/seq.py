@@ -24,7 +24,8 @@ class SequenceStatus(Enum):
 class Sequence:
     __slots__ = ("seq_id", "status", "token_ids", "last_token", "num_tokens", "num_prompt_tokens",
                  "num_cached_tokens", "num_scheduled_tokens", "is_prefill", "block_table", "table_gen",
-                 "temperature", "max_tokens", "ignore_eos", "rng_key", "top_k", "top_p")
+                 "temperature", "max_tokens", "ignore_eos", "rng_key", "top_k", "top_p",
+                 "presence_penalty", "frequency_penalty", "repetition_penalty")
 
     block_size = 256          # set by the engine from Config.kvcache_block_size
     counter = count()
@@ -50,6 +51,9 @@ class Sequence:
         self.ignore_eos = sp.ignore_eos
         self.top_k = max(sp.top_k, 0)
         self.top_p = sp.top_p
+        self.presence_penalty = sp.presence_penalty
+        self.frequency_penalty = sp.frequency_penalty
+        self.repetition_penalty = sp.repetition_penalty
 
     def __len__(self) -> int:
         return self.num_tokens
@@ -108,3 +112,4 @@ class Sequence:
         self.status, self.is_prefill = SequenceStatus.RUNNING, isinstance(payload, list)
         self.temperature, self.max_tokens, self.ignore_eos = 1.0, 0, False
         self.top_k, self.top_p = 0, 1.0
+        self.presence_penalty, self.frequency_penalty, self.repetition_penalty = 0.0, 0.0, 1.0

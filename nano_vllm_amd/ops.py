@@ -80,6 +80,10 @@ SIGNATURES = {
     "nvl_sample_topk_topp": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_int64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "nvl_feed_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "nvl_store_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "nvl_feed_store_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "nvl_apply_penalties": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p]),
     "nvl_allreduce_create": (c_int, [c_int, c_int, c_int64, ctypes.POINTER(c_void_p)]),
     "nvl_allreduce_uid": (c_int, [c_void_p, c_void_p]),
     "nvl_allreduce_connect": (c_int, [c_void_p, c_void_p]),
@@ -935,6 +939,59 @@ def feed_tokens(ids: torch.Tensor, src_row: torch.Tensor, prev_tokens: torch.Ten
     assert ids.dtype == torch.int64 and prev_tokens.dtype == torch.int64 and src_row.dtype == torch.int32
     assert ids.is_contiguous() and src_row.is_contiguous() and src_row.numel() == ids.numel()
     _check(lib().nvl_feed_tokens(ids.data_ptr(), src_row.data_ptr(), prev_tokens.data_ptr(), ids.numel(), _stream()))
+
+
+def _token_cache(token_cache: torch.Tensor, like: torch.Tensor) -> None:
+    assert token_cache.dtype == torch.int32 and token_cache.dim() == 1 and token_cache.is_contiguous() \
+        and token_cache.device == like.device, "token_cache: want a contiguous int32 [num_blocks * block_size] device tensor"
+
+
+def store_tokens(ids: torch.Tensor, slots: torch.Tensor, token_cache: torch.Tensor) -> None:
+    """token_cache[slots[i]] = ids[i] wherever slots[i] >= 0 (int64 ids, int32 slots; the token cache shadows the KV
+    cache slot for slot)."""
+    _dev(ids, "ids")
+    _token_cache(token_cache, ids)
+    assert ids.dtype == torch.int64 and slots.dtype == torch.int32 and ids.is_contiguous() and slots.is_contiguous()
+    assert slots.numel() == ids.numel()
+    _check(lib().nvl_store_tokens(ids.data_ptr(), slots.data_ptr(), token_cache.data_ptr(), token_cache.numel(),
+                                  ids.numel(), _stream()))
+
+
+def feed_store_tokens(ids: torch.Tensor, src_row: torch.Tensor, prev_tokens: torch.Tensor, slots: torch.Tensor,
+                      token_cache: torch.Tensor) -> None:
+    """`feed_tokens` and `store_tokens` of the resolved ids in one launch (first node of a decode step)."""
+    _dev(ids, "ids")
+    _token_cache(token_cache, ids)
+    assert ids.dtype == torch.int64 and prev_tokens.dtype == torch.int64 and src_row.dtype == torch.int32
+    assert slots.dtype == torch.int32 and ids.is_contiguous() and src_row.is_contiguous() and slots.is_contiguous()
+    assert src_row.numel() == ids.numel() and slots.numel() == ids.numel()
+    _check(lib().nvl_feed_store_tokens(ids.data_ptr(), src_row.data_ptr(), prev_tokens.data_ptr(), slots.data_ptr(),
+                                       token_cache.data_ptr(), token_cache.numel(), ids.numel(), _stream()))
+
+
+def apply_penalties(logits: torch.Tensor, token_cache: torch.Tensor, block_tables: torch.Tensor,
+                    context_lens: torch.Tensor, prompt_lens: torch.Tensor, presence: torch.Tensor,
+                    frequency: torch.Tensor, repetition: torch.Tensor, block_size: int, max_context: int) -> torch.Tensor:
+    """Presence / frequency / repetition penalties, in place on bf16 logits [B, V], from the rows' token history in the
+    token cache (include/nvl.h: the formula, its order and the bounds). block_tables int32 [B, W]; context_lens /
+    prompt_lens int32 [B] (context 0: padding row, untouched); the penalties fp32 [B] (0, 0, 1: row untouched)."""
+    _dev(logits, "logits")
+    _token_cache(token_cache, logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype == torch.bfloat16
+    b, vocab = logits.shape
+    assert block_tables.dtype == torch.int32 and block_tables.dim() == 2 and block_tables.stride(1) == 1 \
+        and block_tables.shape[0] >= b and block_tables.device == logits.device
+    for name, t, dt in (("context_lens", context_lens, torch.int32), ("prompt_lens", prompt_lens, torch.int32),
+                        ("presence", presence, torch.float32), ("frequency", frequency, torch.float32),
+                        ("repetition", repetition, torch.float32)):
+        assert t.dtype == dt and t.dim() == 1 and t.is_contiguous() and t.numel() >= b and t.device == logits.device, \
+            f"{name}: want a contiguous {dt} [B] tensor on the logits' device"
+    _check(lib().nvl_apply_penalties(logits.data_ptr(), logits.stride(0), token_cache.data_ptr(), token_cache.numel(),
+                                     block_tables.data_ptr(), block_tables.stride(0), block_tables.shape[1],
+                                     context_lens.data_ptr(), prompt_lens.data_ptr(), presence.data_ptr(),
+                                     frequency.data_ptr(), repetition.data_ptr(), b, vocab, block_size, max_context,
+                                     _stream()))
+    return logits
 
 
 def sample_exponentials_host(seed: int, offset: int, row: int, col0: int, n: int):
